@@ -9,7 +9,10 @@ eval batches of 64 clips exactly as the reference evaluates them: STFT/log-mel +
 audio_proj + L2 -> sound-effect hard prompt -> MLP mapper -> GPT-2 small prefill +
 get_prefix_tokens + greedy generate2 (entry_length 67, stop ids 13 / 764), bf16 operands / f32
 accumulation.  Every decode GEMM of a batch is a 64-row GEMM.  One "step" = one eval batch of
-64 clips (the last batch of the 1045 holds 21).  Independent batches are in flight per GPU, each
+64 clips (the last batch of the 1045 holds 21).  Up to RUN_BATCHES (64) batches are one run of
+the schedule below; a longer job (--steps above 64) is a sequence of near-equal runs inside the
+timed region over the same buffers, its clips cycling over 64 batches of resident waveforms, so
+memory does not grow with --steps.  Independent batches are in flight per GPU, each
 on its own HIP stream (pipeline twins sharing the weights, zsaac/pipeline.py ConcurrentRunner),
 each decoding in its own persistent launch of 48 half-CU workgroups (a larger grid when few
 batches wait, zsaac.pipeline.choose_persist_grid; the grid never changes an id, decode_grid.hip).
@@ -17,8 +20,9 @@ Schedule (--begin-first 1, the default): a pipeline per batch; every batch's beg
 mapper, prefill, get_prefix_tokens, step 0) runs as the encoder's passes deliver, before the
 first decode grid launches; the grids then launch in batch order within --persist-budget slots
 (default 2 x CUs less a sixteenth: ten grids of 48); --begin-first 0 is round 5's pipelined
-schedule (at most --inflight batches, begins beside the grids).  The timed region runs --reps
-times (median reported); GPU_MAX_HW_QUEUES is raised to --hw-queues (default 16, the runtime
+schedule (at most --inflight batches, begins beside the grids).  The timed region runs once,
+so --steps is the number of timed steps (--reps R, and --full, which defaults to 3: R times, the
+median reported); GPU_MAX_HW_QUEUES is raised to --hw-queues (default 16, the runtime
 allows up to 32; streams beyond it share queues in order).  With N ranks the
 clips are sharded (zsaac/dist.py shard_range) and ONE RCCL all-gather of the generated token ids
 + lengths (zsaac/dist.py collect_captions) is inside the timed region.
@@ -27,8 +31,16 @@ clips are sharded (zsaac/dist.py shard_range) and ONE RCCL all-gather of the gen
     python bench.py --steps K                        # K full batches of 64 per rank (weak)
     python bench.py --clips N                        # N clips in total, sharded (strong)
     torchrun --nproc-per-node N bench.py --gpus N    # one process per GPU, RCCL
+    python bench.py --dump-outputs DIR               # + the last timed run's results as DIR/*.npy
+    python bench.py --full                           # + every secondary measurement below
 
-Rank 0 prints ONE JSON line.  Besides the contract fields (value = whole-job clips/s) it holds
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the
+contract fields (value = whole-job clips/s, ms_per_step = the timed region / its steps) with the
+run's configuration.  --dump-outputs DIR then writes what the timed path returned for this rank's
+clips in the last timed repetition (caption_arrays: ids, lengths, hard prompt, prefix ids, CLAP
+embeddings, a row per clip; the clips and weights are seeded, so two builds can be compared array
+for array).  With --full the line also holds (each leg has its own switch: --no-roofline,
+--no-scaling-proxy, --extras 0, --no-cpu-baseline)
   roofline:          the dominant kernel, dg_persist_kernel (zs_gpt2_decode_persist: every
                      decode step after step 0 of one eval batch in one launch), HBM-bound:
                      algorithmic bytes per launch (weights per step + every row's K/V reads and
@@ -153,14 +165,26 @@ def parse(argv=None):
     ap.add_argument("--persist-budget", type=int, default=0,
                     help="workgroup slots (half a CU each) the in-flight persistent decode grids "
                          "may hold together (0: ZSAAC_PERSIST_BUDGET or 1.5 per CU)")
-    ap.add_argument("--reps", type=int, default=HEADLINE_REPS,
-                    help="timed repetitions of the headline region (value = their median)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions of the headline region (value = their median; "
+                         f"default 1, so --steps is the number of timed steps; {HEADLINE_REPS} "
+                         "with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else this file reports: "
+                         "rooflines and per-stage times, the 1045-clip set and the strong-scaling "
+                         "proxy, the f32 / throughput / C3 / C5 configurations, id agreement and "
+                         "the CPU baseline (each can be switched off by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed repetition returned to its caller (token ids, "
+                         "lengths, prompts, CLAP embeddings; --embeddings-only: the embeddings) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all")
     ap.add_argument("--hw-queues", type=int, default=16,
                     help="GPU_MAX_HW_QUEUES for this process (read before HIP initialises)")
     ap.add_argument("--compact", type=int, default=1,
                     help="greedy bf16 at >= 512 rows: decode only the rows that have not stopped")
     ap.add_argument("--extras", type=int, default=1,
-                    help="N=1: also measure the throughput mode, the f32 mode and id agreement")
+                    help="--full at N=1: 0 leaves out the throughput, f32, C3 and C5 "
+                         "configurations and id agreement")
     ap.add_argument("--cpu-baseline-clips", type=int, default=32,
                     help="C2 clips timed on the CPU oracle (C1: all 50 golden clips, C3 beam 5: "
                          "a quarter of this, at least 4)")
@@ -231,6 +255,58 @@ def synthetic_clips(n, first, device):
     return out
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_BYTES = 64 * 10 ** 6        # files and their .npy headers together
+
+
+def dump_arrays(path, arrays, seed=0):
+    """Writes ``arrays`` ({name: array with one row per clip}) as path/<name>.npy in float32.
+    Above DUMP_MAX_BYTES in all, the same seeded sample of the rows (ascending, also written as
+    rows.npy) is kept of every array."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(1, n) for a in arrays.values()) + 4
+    keep = (DUMP_MAX_BYTES - 256 * (len(arrays) + 1)) // row_bytes
+    if n > keep:
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log(f"wrote {sorted(arrays)} to {path} ({sum(a.nbytes for a in arrays.values())} bytes)")
+
+
+def caption_arrays(outs):
+    """The CaptionBatch results of a run (one per eval batch, in clip order) as one array per
+    field with a row per clip: ids / lengths (beam: per beam, with scores), the hard prompt,
+    get_prefix_tokens' ids and the CLAP embedding.  Entries past a row's own length are not
+    results (buffers are reused): they are written as -1."""
+    import numpy as np
+
+    def cat(field, length=None):
+        parts = []
+        for o in outs:
+            a = getattr(o, field).float().cpu().numpy()
+            if length is not None:
+                ln = getattr(o, length).cpu().numpy()
+                a = np.where(np.arange(a.shape[-1]) < ln[..., None], a, -1.0)
+            parts.append(a)
+        w = max(p.shape[-1] for p in parts) if parts[0].ndim > 1 else 0
+        parts = [np.pad(p, [(0, 0)] * (p.ndim - 1) + [(0, w - p.shape[-1])], constant_values=-1.0)
+                 if p.ndim > 1 else p for p in parts]
+        return np.concatenate(parts)
+    res = {"ids": cat("ids", "lengths"), "lengths": cat("lengths"),
+           "hard_ids": cat("hard_ids", "hard_len"), "hard_len": cat("hard_len"),
+           "plen": cat("plen"), "clap_emb": cat("clap_emb")}
+    if outs[0].scores is not None:
+        res["scores"] = cat("scores")
+    if outs[0].prefix_ids is not None:
+        res["prefix_ids"] = cat("prefix_ids", "plen")
+    return res
+
+
 # ------------------------------------------------------------------ caption runs
 def split_batches(n, B, parts=0):
     """[start, end) ranges of n clips in eval batches of at most B: consecutive full batches (the
@@ -246,6 +322,25 @@ def split_batches(n, B, parts=0):
     for j in range(k):
         b = a + base + (1 if j < rem else 0)
         out.append((a, b))
+        a = b
+    return out
+
+
+# eval batches one ConcurrentRunner.run takes: the staged schedule holds a begin group's buffers
+# (about 2.5 GB per 2 batches) for every batch of a run, and the waveforms are resident (82 MB per
+# batch), so a longer job is a sequence of runs over the same buffers.  A run's fixed cost is
+# about 3 ms (0.159 s at 20 batches, 0.315 s at 40), under 1 % of a run of 64
+RUN_BATCHES = 64
+
+
+def split_runs(batches):
+    """Consecutive near-equal runs of at most RUN_BATCHES batches (one run up to RUN_BATCHES)."""
+    k = max(1, -(-len(batches) // RUN_BATCHES))
+    base, rem = divmod(len(batches), k)
+    out, a = [], 0
+    for j in range(k):
+        b = a + base + (1 if j < rem else 0)
+        out.append(batches[a:b])
         a = b
     return out
 
@@ -277,15 +372,23 @@ def run_captions(args, world, rank, device, pipe, n_local, first, counts, inflig
                  parts=0, log_pass=False, reps=1):
     """Times the captioning of this rank's n_local clips (clip ids first..) in batches of
     pipe.cfg.batch (split_batches) on `inflight` streams, then the all-gather; returns (seconds
-    max over ranks, outs, runner, info)."""
+    max over ranks, outs, runner, info).  Memory does not grow with n_local past RUN_BATCHES
+    batches: the runner takes them in consecutive runs of at most RUN_BATCHES (split_runs), all
+    inside the timed region, and clip c reads waveform c modulo RUN_BATCHES batches."""
     from zsaac.pipeline import ConcurrentRunner, persist_budget
     from zsaac import decoder as zdec, dist as zd
     B = pipe.cfg.batch
-    pool = synthetic_clips(n_local, first, device)
-    batches = [pool[a:b] for a, b in split_batches(n_local, B, parts)]
-    log(f"{n_local} clips in {len(batches)} batches of <= {B}, {inflight} in flight: capturing")
+    clips = synthetic_clips(min(n_local, RUN_BATCHES * B), first, device)
+    P = clips.shape[0]
+    if parts and n_local > P:
+        raise ValueError(f"balanced batches need the whole set resident (<= {P} clips)")
+    batches = [clips[a % P:a % P + (b - a)] for a, b in split_batches(n_local, B, parts)]
     if len(batches) == 0:
         raise ValueError("no clips on this rank")
+    runs = split_runs(batches)
+    per_run = max(len(r) for r in split_runs(list(range(max(len(batches), warmup)))))
+    log(f"{n_local} clips in {len(batches)} batches of <= {B} ({len(runs)} runs of <= {per_run}), "
+        f"{inflight} in flight: capturing")
     ahead = getattr(args, "encode_ahead", 0)
     if getattr(args, "beam", 0) or ahead < B:      # beam runs / larger batches: encoder per batch
         ahead = 0
@@ -298,7 +401,7 @@ def run_captions(args, world, rank, device, pipe, n_local, first, counts, inflig
     bgroup = int(getattr(args, "begin_group", 2)) if bfirst and args.mapper == "mlp" else 0
     if bfirst:
         if not bgroup:          # a pipeline per batch: every begin runs before the grids
-            inflight = max(inflight, len(batches))
+            inflight = max(inflight, per_run)
         budget = budget or persist_budget(torch.cuda.get_device_properties(device).multi_processor_count,
                                           staged=True)
     nstreams = max(1, inflight) + extra
@@ -311,12 +414,13 @@ def run_captions(args, world, rank, device, pipe, n_local, first, counts, inflig
                               encode_ahead=ahead, enc_stream=enc_stream(device) if ahead else None,
                               extra_pipes=extra, cu_split=getattr(args, "cu_split", 0),
                               begin_first=bfirst, begin_gate=getattr(args, "begin_gate", 0),
-                              begin_group=bgroup, n_batches=len(batches))
+                              begin_group=bgroup, n_batches=per_run)
     for size in sorted({b.shape[0] for b in batches}, reverse=True):   # captures every graph
         runner.warmup(next(b for b in batches if b.shape[0] == size))
         log(f"captured the decode graphs of {size}-clip batches")
     if warmup:
-        runner.run([batches[i % len(batches)] for i in range(warmup)])
+        for r in split_runs([batches[i % len(batches)] for i in range(warmup)]):
+            runner.run(r)
         log(f"warmed up ({warmup} batches)")
     torch.cuda.synchronize()
     if world > 1:
@@ -327,7 +431,13 @@ def run_captions(args, world, rank, device, pipe, n_local, first, counts, inflig
     times, gave_up = [], 0
     for _ in range(reps):          # every repetition the whole region; the median is reported
         t0 = time.perf_counter()
-        outs = runner.run(batches)
+        outs, dsteps, grids = [], [], {}
+        for r in runs:
+            outs += runner.run(r)
+            dsteps += runner.decode_steps
+            gave_up += getattr(runner, "gave_up", 0)
+            for k, v in grid_counts(runner).items():
+                grids[k] = grids.get(k, 0) + v
         if world > 1:
             zd.collect_captions(outs, counts)
         torch.cuda.synchronize()
@@ -340,19 +450,20 @@ def run_captions(args, world, rank, device, pipe, n_local, first, counts, inflig
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             dt_r = float(t)
         times.append(dt_r)
-        gave_up += getattr(runner, "gave_up", 0)
     rows1 = sum(d.rows_stepped for d in runner.decoders())     # (before the log pass)
     dt = sorted(times)[len(times) // 2]
     log(f"timed: {n_local} clips in {dt:.3f} s (median of {reps}: {[round(t, 4) for t in times]})")
     if gave_up:
         log(f"WARNING: {gave_up} persistent launches gave up and finished on the phase launches")
     runner.timed_log, runner.log_outs = [], None
+    runner.log_share = len(runs[-1]) / len(batches)
     if log_pass and pipe.decoder.persist:
-        # the roofline's live launch timing: the same batches once more, untimed, with HIP events
-        # around every persistent launch (events recorded inside the timed region cost it 3-5 %)
+        # the roofline's live launch timing: the same batches (the last run's) once more, untimed,
+        # with HIP events around every persistent launch (events recorded inside the timed region
+        # cost it 3-5 %)
         zdec.PERSIST_LOG = []
         try:
-            runner.log_outs = runner.run(batches)
+            runner.log_outs = runner.run(runs[-1])
             torch.cuda.synchronize()
             runner.timed_log = list(zdec.PERSIST_LOG)
         finally:
@@ -361,7 +472,8 @@ def run_captions(args, world, rank, device, pipe, n_local, first, counts, inflig
     info = {"graph_captures_timed": sum(d.n_captures for d in runner.decoders()) - cap0,
             "timed_reps_s": [round(t, 5) for t in times],
             "persist_gave_up": gave_up,
-            "persist_grids": grid_counts(runner),
+            "persist_grids": grids,
+            "runs": len(runs), "batches_per_run": max(len(r) for r in runs),
             "persist_budget_wg_slots": getattr(runner, "budget", None),
             "batches_in_flight": runner.n_inflight,
             "schedule": (("begin_first: " + (f"one begin per {runner.begin_group} eval batches "
@@ -370,14 +482,14 @@ def run_captions(args, world, rank, device, pipe, n_local, first, counts, inflig
                                              if runner.begin_group else "a pipeline per batch")
                           + ", every begin before the first grid launches, grids launched as the "
                             "budget frees")
-                         if getattr(runner, "begin_first", False) and len(batches) > runner.budget // runner.grids[-1]
+                         if getattr(runner, "begin_first", False) and len(runs[0]) > runner.budget // runner.grids[-1]
                          else "pipelined: begins beside the decode grids"),
             # decode rows stepped per clip in ONE repetition of the timed region
             "decode_rows_stepped_per_clip": round((rows1 - rows0) / max(1, reps) / max(1, n_local), 2),
-            "decode_steps_mean": round(sum(runner.decode_steps) / max(1, len(runner.decode_steps)), 2),
+            "decode_steps_mean": round(sum(dsteps) / max(1, len(dsteps)), 2),
             "tokens_rank0": int(sum(int(o.lengths.sum()) if o.scores is None
                                     else int(o.lengths[:, 0].sum()) for o in outs))}
-    del pool
+    del clips
     return dt, outs, runner, info
 
 
@@ -902,6 +1014,8 @@ def main_embeddings(args, world, rank, device, pipe):
            "config": {"workload": "C4 embedding extraction, RCCL all-gather of [N,1024] f32",
                       "encoder_batch": B, "clips_total": n_total, "clips_per_rank": counts,
                       "parallelism": f"dp{world} (clip-sharded)"}}
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_arrays(args.dump_outputs, {"clap_emb": gathered[0].float().cpu().numpy()})
     if rank == 0:
         print(json.dumps(res), flush=True)
     return res, gathered[0]
@@ -1246,6 +1360,10 @@ def strong_scaling_proxy(args, device, pipe, t_full, n_full, n_ranks=8, full_src
 
 def main():
     args = parse()
+    full = args.full
+    if args.dump_outputs and (args.magic or args.mistral):
+        raise SystemExit("--dump-outputs covers the caption runs and --embeddings-only")
+    reps = max(1, args.reps if args.reps is not None else (HEADLINE_REPS if full else 1))
     world, rank, local = dist_setup(args)
     device = torch.device("cuda", local)
     from zsaac import dist as zd
@@ -1271,11 +1389,14 @@ def main():
         counts = [per] * world
     n_local = hi - lo
     steps = -(-n_local // B)
-    want_roof = (rank == 0 and not args.no_roofline and args.group == 1 and B <= 64
+    want_roof = (full and rank == 0 and not args.no_roofline and args.group == 1 and B <= 64
                  and not args.beam and args.dtype == "bf16")
     dt, outs, runner, info = run_captions(args, world, rank, device, pipe, n_local, lo, counts,
                                           args.inflight, args.warmup, log_pass=want_roof,
-                                          reps=max(1, args.reps))
+                                          reps=reps)
+    log(f"peak device memory {torch.cuda.max_memory_allocated(device) / 2 ** 30:.1f} GiB")
+    if rank == 0 and args.dump_outputs:          # this rank's clips, the last timed repetition
+        dump_arrays(args.dump_outputs, caption_arrays(outs))
     workload = (("C3 AudioCaps-eval" if args.beam else "C2 Clotho-eval")
                 + (" (1045 clips per rank)" if not (args.steps or args.clips) else "")
                 + ": STFT/log-mel + " + args.encoder.upper() + " + " + args.mapper
@@ -1313,14 +1434,14 @@ def main():
     if info["persist_gave_up"]:
         res["warning"] = (f"{info['persist_gave_up']} persistent decode launches gave up (grid "
                           "not co-resident) and finished on the phase launches")
-    if world > 1 and not args.clips and args.group == 1 and not args.beam:
+    if full and world > 1 and not args.clips and args.group == 1 and not args.beam:
         # strong scaling on the Clotho-eval set itself: its 1045 clips sharded over the ranks
         # (what north_star's ">= 6x from 1 to 8 GPUs on Clotho-eval" measures), timed beside the
         # weak-scaling value
         slo, shi = zd.shard_range(CLOTHO_EVAL_CLIPS, rank, world)
         scounts = zd.shard_counts(CLOTHO_EVAL_CLIPS, world)
         dts, _, srun, sinfo = run_captions(args, world, rank, device, pipe, shi - slo, slo, scounts,
-                                           args.inflight, 1, reps=max(1, args.reps))
+                                           args.inflight, 1, reps=reps)
         res["strong_1045"] = {"value": round(CLOTHO_EVAL_CLIPS / dts, 2), "unit": "clips/s",
                               "clips_total": CLOTHO_EVAL_CLIPS, "clips_per_rank": scounts,
                               "seconds": round(dts, 5), "timed_reps_s": sinfo["timed_reps_s"],
@@ -1328,11 +1449,12 @@ def main():
                               "grids_rank0": sinfo["persist_grids"]}
         del srun
     headline_cfg = rank == 0 and args.group == 1 and B <= 64 and not args.beam
-    if rank == 0 and not args.no_roofline and headline_cfg and args.dtype == "bf16":
+    if full and rank == 0 and not args.no_roofline and headline_cfg and args.dtype == "bf16":
         log("rooflines")
         from zsaac import decoder as zdec
         if pipe.decoder.persist:
-            res["roofline"] = persist_roofline(pipe, runner, runner.log_outs, dt, runner.timed_log)
+            res["roofline"] = persist_roofline(pipe, runner, runner.log_outs, dt * runner.log_share,
+                                               runner.timed_log)
         else:
             res["roofline"] = roofline_gemm_ln(pipe)
         wav = synthetic_clips(B, 0, device)
@@ -1350,7 +1472,7 @@ def main():
     elif rank == 0 and args.stages:
         res["stages"] = stage_times(pipe, synthetic_clips(B, 0, device))
     t_full = None
-    if rank == 0 and world == 1 and headline_cfg and not args.clips:
+    if full and rank == 0 and world == 1 and headline_cfg and not args.clips:
         # the metric's own set: the 1045-clip Clotho-eval set, the headline itself when it ran on
         # it, else timed here (median of 3) when --steps sized the headline differently
         if n_total == CLOTHO_EVAL_CLIPS:
@@ -1362,7 +1484,7 @@ def main():
         res["clotho_1045"] = {"value": round(CLOTHO_EVAL_CLIPS / t_full, 2), "unit": "clips/s",
                               "clips": CLOTHO_EVAL_CLIPS, "seconds": round(t_full, 5),
                               "timed_reps_s": c_reps, "source": c_src}
-    if (rank == 0 and world == 1 and headline_cfg and not args.clips
+    if (full and rank == 0 and world == 1 and headline_cfg and not args.clips
             and not args.no_scaling_proxy):
         # on the 1045-clip Clotho-eval set (clotho_1045 above)
         res["strong_scaling_proxy"] = strong_scaling_proxy(
@@ -1377,7 +1499,7 @@ def main():
         gc.collect()
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.extras and args.group == 1 and not args.beam:
+    if full and rank == 0 and world == 1 and args.extras and args.group == 1 and not args.beam:
         del pipe
         release()
         log("f32 parity mode")
@@ -1404,7 +1526,8 @@ def main():
         res["id_agreement"] = {"bench_weights": BENCH_WEIGHTS_GOLDEN,
                                "bf16": idparity.summary(torch.bfloat16, device),
                                "f32": idparity.summary(torch.float32, device)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_baseline_clips > 0:
+    if (full and rank == 0 and world == 1 and not args.no_cpu_baseline
+            and args.cpu_baseline_clips > 0):
         n2, n1, n3 = ((64, 50, 64) if args.cpu_baseline_full else
                       (args.cpu_baseline_clips, 50, max(4, args.cpu_baseline_clips // 4)))
         res["cpu_baseline"] = cpu_baseline(args, csd, asd, n2, n1, n3)

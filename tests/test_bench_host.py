@@ -15,6 +15,16 @@ def test_split_batches_reference_and_balanced():
     assert bench.split_batches(3, 64, parts=5) == [(0, 1), (1, 2), (2, 3)]
 
 
+def test_split_runs_bounded_and_in_order():
+    """A job is one run up to RUN_BATCHES batches, beyond it consecutive near-equal runs."""
+    R = bench.RUN_BATCHES
+    for n in (1, 20, R, R + 1, 3 * R, 10 * R + 7):
+        runs = bench.split_runs(list(range(n)))
+        assert [b for r in runs for b in r] == list(range(n))
+        assert len(runs) == -(-n // R) and max(map(len, runs)) - min(map(len, runs)) <= 1
+        assert max(map(len, runs)) <= R
+
+
 def test_persist_launch_bytes():
     row = 12 * 2 * 768 * 2
     # 2 rows, prompt 10 and 12, 3 steps (steps 1, 2 in the launch): step t at position
@@ -22,6 +32,52 @@ def test_persist_launch_bytes():
     got = bench.persist_launch_bytes(1000, [10, 12], 3)
     assert got == 2 * 1000 + row * ((10 + 11) + (12 + 13) + 2 * 2)
     assert bench.persist_launch_bytes(1000, [10], 1) == 0
+
+
+def test_plain_run_options():
+    """A plain run times the steps once and measures nothing else; --full is off by default."""
+    a = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert (a.full, a.reps, a.dump_outputs, a.steps, a.warmup) == (False, None, None, 4, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: a row per clip across eval batches, entries past a row's length -1,
+    float32 files, and above the size limit the same seeded rows of every array."""
+    import numpy as np
+    import torch
+    from zsaac.pipeline import CaptionBatch
+
+    def batch(n, first):
+        ids = torch.arange(first, first + n * 6, dtype=torch.int32).view(n, 6)
+        return CaptionBatch(ids=ids, lengths=torch.full((n,), 3, dtype=torch.int32), scores=None,
+                            hard_ids=torch.ones(n, 4, dtype=torch.int32),
+                            hard_len=torch.full((n,), 2, dtype=torch.int32),
+                            plen=torch.full((n,), 5, dtype=torch.int32),
+                            prefix_ids=torch.ones(n, 7, dtype=torch.int32),
+                            clap_emb=torch.ones(n, 8).bfloat16())
+    arr = bench.caption_arrays([batch(2, 0), batch(1, 100)])
+    assert arr["ids"].tolist() == [[0, 1, 2, -1, -1, -1], [6, 7, 8, -1, -1, -1],
+                                   [100, 101, 102, -1, -1, -1]]
+    assert arr["lengths"].tolist() == [3, 3, 3] and arr["clap_emb"].shape == (3, 8)
+    assert arr["hard_ids"][0].tolist() == [1, 1, -1, -1]
+    assert arr["prefix_ids"][2].tolist() == [1, 1, 1, 1, 1, -1, -1]
+    bench.dump_arrays(str(tmp_path / "all"), arr)
+    got = {f.name: np.load(f) for f in (tmp_path / "all").iterdir()}
+    assert sorted(got) == sorted(k + ".npy" for k in arr)
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["ids.npy"], arr["ids"])
+    row = sum(v.nbytes // 3 for v in arr.values()) + 4
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * row + 256 * (len(arr) + 1))
+    for d in ("s1", "s2"):
+        bench.dump_arrays(str(tmp_path / d), arr)
+    s1 = {f.name: np.load(f) for f in (tmp_path / "s1").iterdir()}
+    rows = s1["rows.npy"].astype(int)
+    assert len(rows) == 2
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(s1["ids.npy"], arr["ids"][rows])
+    assert all(np.array_equal(v, np.load(tmp_path / "s2" / k)) for k, v in s1.items())
 
 
 def test_choose_persist_grid_keeps_grids_coresident():
