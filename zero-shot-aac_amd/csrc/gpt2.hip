@@ -55,11 +55,14 @@ __device__ __forceinline__ void label_select_k(const float* __restrict__ emb, in
   for (int i = 0; i < PK_MAX; ++i) sel[i] = 0x7fffffff;
   auto insert = [&](float sv, int l) {          // strictly better only: ties keep the earlier
     if (K != PK_MAX && !(sv > tv[K - 1])) return;   // (K == k: below the k-th best)
+    bool placed = false;   // once placed, every entry below moves down one: a displaced entry
+                           // stays ahead of the equal entries (of higher index) below it
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-      if (i < k && sv > tv[i]) {
+      if (i < k && (placed || sv > tv[i])) {
         const float t = tv[i]; const int ti = sel[i];
         tv[i] = sv; sel[i] = l; sv = t; l = ti;
+        placed = true;
       }
     }
   };
