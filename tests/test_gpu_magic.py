@@ -117,6 +117,25 @@ def test_magic_search_f32_bit_exact(cuda, gold):
         assert outs[k] == gold["search_ids"][k, :gold["search_len"][k]].tolist(), k
 
 
+def test_magic_search_f32_batched_ragged_steps(cuda, gold):
+    """All three clips in one search call with decoding_len = 25: the prompts are 17, 19 and 17
+    rows, so the clips run 8, 6 and 8 steps in one batch (a per-clip step limit: the middle clip
+    is frozen while the others go on).  The goldens (10 steps per clip) contain no stop token, so
+    their prefixes are the expected ids."""
+    from zsaac.tokenizer import WordTokenizer
+    C = gold["clap_emb"].shape[0]
+    eng, clap, csd = _engine(cuda, gold, torch.float32, 2.0, 1, 15, 12, C)
+    hard, hl, soft, emb = _inputs(cuda, gold, csd)
+    P = (hl.cpu() + 10).tolist()
+    assert P == [17, 19, 17]
+    steps = [25 - p for p in P]
+    assert 13 not in gold["search_ids"] and all(gold["search_len"][k] >= steps[k] for k in range(C))
+    outs = eng.search(hard, hl, soft, 10, emb, WordTokenizer(), clap.text_encoder.tokenizer,
+                      width=15, decoding_len=25, alpha=0.1, beta=0.2, temp=float(clap.temp))
+    for k in range(C):
+        assert outs[k] == gold["search_ids"][k, :steps[k]].tolist(), k
+
+
 def test_dropin_generate_beam_magic(cuda, gold):
     """gpt2_prefix_eval.generate_beam_magic / magic_search called like predict_prompt.py:140."""
     import gpt2_prefix_eval as G

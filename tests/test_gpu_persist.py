@@ -106,6 +106,41 @@ def test_full_batch_of_64(cuda):
     assert idparity.agreement(g, caps[:32])["exact_frac"] == 1.0
 
 
+def test_graph_capture_saves_state_before_its_warmup_step(cuda):
+    """Capturing the chunk graph runs one warm-up step on a side stream, with the decode state
+    saved before it and restored after it.  The save has to be complete before that step may
+    start.  Here every copy of the save after the first (pos) is held back 20 ms on the caller's
+    stream: a warm-up step that waits only for the work enqueued before the save runs meanwhile,
+    the save then mixes pos from before the step with a step counter from after it, and the run
+    ends with pos one short (seen once as test_full_batch_of_64 failing on 'pos' by exactly 1 in
+    every row, when another process delayed the caller's queue at that point)."""
+    from tools import idparity
+    from zsaac import ops
+    g = idparity.load("c2_margin_flat")
+    emb = torch.from_numpy(g["clap_emb"][:16]).to(cuda)
+    p = _pipe(g, cuda, False, batch=16)
+    ref_caps = p.caption_emb(emb).captions()
+    ref = _state(p, 16)
+    d = p.decoder
+    d.graphs.clear()
+    plain, calls = d._state, []
+
+    def held_back():
+        first = not calls
+        calls.append(1)
+        for i, t in enumerate(plain()):
+            yield t
+            if first and i == 0:
+                ops.stream_spin(20000)
+    d._state = held_back
+    caps = p.caption_emb(emb).captions()
+    st = _state(p, 16)
+    assert len(calls) == 2, "the chunk graph was not captured again (save + restore)"
+    assert caps == ref_caps
+    for k in ref:
+        assert np.array_equal(st[k], ref[k]), k
+
+
 @pytest.mark.parametrize("B", [1, 7, 21])
 def test_ragged_batches(cuda, B):
     from tools import idparity

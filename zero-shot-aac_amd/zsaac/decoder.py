@@ -575,8 +575,10 @@ class Gpt2Decoder:
             if getattr(self, "_cap_stream", None) is None:
                 self._cap_stream = torch.cuda.Stream()    # one side stream per decoder
             s = self._cap_stream
-            s.wait_stream(cur)
+            # the save first: the warm-up step may only start once every copy is done (it rewrites
+            # pos, the step counter, ...; a save that overlapped it restored a mixed state)
             saved = [t.clone() for t in self._state()]
+            s.wait_stream(cur)
             with torch.cuda.stream(s):
                 if pre is not None:
                     pre()
