@@ -335,13 +335,18 @@ int zs_mistral_embed(const int* hard, int H, const float* soft, int ns, const in
                      void* stream);
 
 /* zs_mistral_add_rmsnorm: x[m] += sum_s y[s][m] (y may be NULL), h[m] = w * (x[m] *
- * rsqrt(mean(x[m]^2) + eps)) (MistralRMSNorm; w NULL = folded into the next GEMM). */
+ * rsqrt(mean(x[m]^2) + eps)) (MistralRMSNorm; w NULL = folded into the next GEMM).  x f32 [M][D]
+ * updated in place (untouched when y is NULL), h [M][D] in hdtype; D % 4 == 0, D <= 16384,
+ * ss % 4 == 0, x / y / h 16-byte aligned (checked). */
 int zs_mistral_add_rmsnorm(float* x, const float* y, int nsplit, long ss, int M, int D, float eps,
                            const float* w, void* h, int hdtype, void* stream);
 
 /* zs_mistral_rope_kv: q|k|v slabs [nsplit][M][(H + 2 KVH) * 128] -> rotary-embedded q [M][H*128]
  * and k, plus v, appended to the caches [seq][KVH][Lmax][128] at position pos[m] (seq =
- * m / rows_per_seq); cos / sin [Lmax][64] f32 tables (HF rotary, rotate_half). */
+ * m / rows_per_seq); cos / sin [Lmax][64] f32 tables (HF rotary, rotate_half).  Element-wise
+ * accesses: no alignment requirement beyond the element type, any ss.  The caller guarantees
+ * 0 <= pos[m] < Lmax and caches of ceil(M / rows_per_seq) sequences (pos is device memory: not
+ * checked); only rows pos[m] of the caches are written. */
 int zs_mistral_rope_kv(const float* qkv, int nsplit, long ss, int M, int H, int KVH,
                        const int* pos, int rows_per_seq, const float* cosb, const float* sinb,
                        void* q, void* kc, void* vc, int Lmax, int dtype, void* stream);
@@ -354,7 +359,9 @@ int zs_fp8_unpack_bf16(const void* W8, int N, int K, void* out, void* stream);
 int zs_scale_cols(float* x, int M, int N, int ld, const float* scale, void* stream);
 
 /* zs_mistral_silu_mul: act[m][f] = silu(gate) * up from gate|up slabs [nsplit][M][2F] whose
- * columns are glu-interleaved: gate f at 16 (f / 8) + 8 (f / 4 % 2) + f % 4, up f at that + 4. */
+ * columns are glu-interleaved: gate f at 16 (f / 8) + 8 (f / 4 % 2) + f % 4, up f at that + 4.
+ * act [M][F] dense in dtype; F % 8 == 0 (so the M F / 4 four-column items are exact), ss % 4 == 0,
+ * gu and act 16-byte aligned (checked). */
 int zs_mistral_silu_mul(const float* gu, int nsplit, long ss, int M, int F, void* act, int dtype,
                         void* stream);
 

@@ -233,7 +233,11 @@ def test_dropin_clap_caption_mistralai(cuda, golden):
 def test_decode_attention_fused_vs_unfused(cuda, dt):
     """zs_mistral_decode_attention (RoPE + KV append + attention in one launch, the decode step)
     against zs_mistral_rope_kv + zs_mistral_attention on the same slabs and caches: identical
-    cache rows, outputs within f32 reassociation (the key p term joins the softmax last)."""
+    cache rows, outputs within f32 reassociation (the key p term joins the softmax last).
+    A consistency check only: both sides share the scale, the head mapping, the reductions and
+    the online softmax, and the random caches hide a read past pos.  Each of the three kernels
+    is compared with a float64 reference in tests/test_gpu_mistral_kernels.py (test_rope_kv,
+    test_attention, test_attention_online_softmax, test_decode_attention)."""
     from zsaac import ops
     from zsaac._lib import call
     M, H, KVH, Lmax, ns = 5, 8, 2, 40, 3

@@ -1084,8 +1084,12 @@ extern "C" int zs_mistral_rope_kv(const float* qkv, int nsplit, long ss, int M, 
                                   const int* pos, int rows_per_seq, const float* cosb,
                                   const float* sinb, void* q, void* kc, void* vc, int Lmax,
                                   int dtype, void* stream) {
-  ZS_REQUIRE(M > 0 && H > 0 && KVH > 0 && H % KVH == 0 && rows_per_seq > 0 && nsplit >= 1,
+  ZS_REQUIRE(M > 0 && H > 0 && KVH > 0 && H % KVH == 0 && rows_per_seq > 0 && nsplit >= 1 &&
+                 Lmax > 0,
              "zs_mistral_rope_kv: bad shape");
+  // element-wise loads and stores: no alignment beyond the element's; pos[m] < Lmax is the
+  // caller's contract (pos lives on the device)
+  ZS_REQUIRE(qkv && pos && cosb && sinb && q && kc && vc, "zs_mistral_rope_kv: NULL buffer");
   const dim3 grid(M, H + 2 * KVH);
   if (dtype == ZS_BF16)
     hipLaunchKernelGGL(mistral_rope_kv_kernel<bf16_t>, grid, dim3(128), 0, S(stream), qkv, nsplit,
@@ -1101,10 +1105,10 @@ extern "C" int zs_mistral_rope_kv(const float* qkv, int nsplit, long ss, int M, 
 
 extern "C" int zs_mistral_silu_mul(const float* gu, int nsplit, long ss, int M, int F, void* act,
                                    int dtype, void* stream) {
-  ZS_REQUIRE(M > 0 && F > 0 && nsplit >= 1, "zs_mistral_silu_mul: bad shape");
+  ZS_REQUIRE(M > 0 && F > 0 && nsplit >= 1 && gu && act, "zs_mistral_silu_mul: bad shape");
   ZS_REQUIRE(F % 8 == 0 && ss % 4 == 0 && ((uintptr_t)gu & 15) == 0 && ((uintptr_t)act & 15) == 0,
              "zs_mistral_silu_mul: F %% 8, the split stride %% 4, 16-byte aligned buffers");
-  const int nb = cdiv((long)M * F / 4, 256);
+  const int nb = cdiv((long)M * F / 4, 256);        // F % 8 == 0: M F / 4 is exact
   if (dtype == ZS_BF16)
     hipLaunchKernelGGL(mistral_silu_mul_kernel<bf16_t>, dim3(nb), dim3(256), 0, S(stream), gu,
                        nsplit, ss, M, F, (bf16_t*)act);
