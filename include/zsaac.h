@@ -62,14 +62,17 @@ int zs_stream_spin(int us, void* stream);
  * window[1024], twiddle[1024] = (cos, sin)(-2*pi*k/1024) interleaved for k < 512 (the DFT is a
  * radix-4 FFT in LDS, two real frames packed per complex FFT), melW[64][513] (librosa.filters.mel, row m nonzero on
  * [mel_lo[m], mel_hi[m])), bn_{mean,var,weight,bias}[64] (eval BatchNorm, eps 1e-5; pass NULL
- * bn_mean to skip bn0). */
+ * bn_mean to skip bn0).  Accepts B > 0, T > 512 (the reflection reads sample 512), B * n_frames
+ * within an int; every other buffer non-NULL. */
 int zs_logmel(const float* wav, int B, int T, const float* window, const float* twiddle,
               const float* melW,
               const int* mel_lo, const int* mel_hi, const float* bn_mean, const float* bn_var,
               const float* bn_weight, const float* bn_bias, float* out, void* stream);
 
 /* zs_wav2img: htsat.py:908-923 reshape_wav2img — bicubic (A=-0.75, align_corners=True) resize of
- * the time axis T_in -> 1024 and fold (B,1,1024,64) -> (B,256,256).  in [B][T_in][64] f32. */
+ * the time axis T_in -> 1024 and fold (B,1,1024,64) -> (B,256,256).  in [B][T_in][64] f32.
+ * Accepts 0 < B <= 32767 (B * 65536 within an int), 1 < T_in <= 1024 (T_in = 1024 copies);
+ * non-NULL buffers. */
 int zs_wav2img(const float* in, int B, int T_in, float* img, void* stream);
 
 /* zs_pack_clips: ragged mono clips (clip b = flat[offsets[b] .. offsets[b] + lengths[b])) ->
@@ -80,14 +83,18 @@ int zs_pack_clips(const float* flat, const long* offsets, const int* lengths, in
                   float* out, void* stream);
 
 /* zs_patch_embed: htsat.py:115-125 PatchEmbed (Conv2d 1->96, k4 s4) + LayerNorm(96):
- * img [B][256][256] f32 -> x [B*4096][96] f32 (token = row*64 + col of the 64x64 patch grid). */
+ * img [B][256][256] f32 -> x [B*4096][96] f32 (token = row*64 + col of the 64x64 patch grid).
+ * Accepts 0 < B <= 32767; non-NULL buffers. */
 int zs_patch_embed(const float* img, int B, const float* w /*[96][16]*/, const float* b,
                    const float* ln_w, const float* ln_b, float* x, void* stream);
 
 /* ------------------------------------------------------------------ generic building blocks
  * zs_layernorm: y[m] = LN(x[rows ? rows[m] : m]) * w + b over C (eps), x f32, y in `ydtype`
  * (ZS_F32/ZS_BF16).  `rows` (int32, may be NULL) gathers rows, e.g. GPT-2 ln_f on the last
- * prompt position of every ragged row. */
+ * prompt position of every ragged row (an index may repeat).  M >= 0 (M == 0 does nothing),
+ * C > 0, ldx >= C, ldy >= C.  Any C, leading dimension and alignment is accepted: rows of
+ * C % 4 == 0, C <= 1024 with ldx % 4 == ldy % 4 == 0 and x, w, b 16-byte (y: 16-byte f32, 8-byte
+ * bf16) aligned take the one-pass register kernel, everything else the strided kernel. */
 int zs_layernorm(const float* x, int M, int C, int ldx, const int* rows, const float* w,
                  const float* b, float eps, void* y, int ldy, int ydtype, void* stream);
 
@@ -134,7 +141,11 @@ int zs_l2norm_rows(const float* x, int M, int C, float eps, float* y, void* stre
  * cyclic roll (htsat.py:443-463), window partition/reverse and the -100 shift mask (406-425)
  * folded into the indexing.  qkv [B*H*W][3C] (dtype) in natural token order; out [B*H*W][C]
  * (dtype) in natural token order.  head_dim = C/heads (24 in HTSAT), ws*ws == 64.
- * rel_table [(2ws-1)^2][heads] f32. */
+ * rel_table [(2ws-1)^2][heads] f32.
+ * Accepts ws == 8, H and W multiples of 8 (H != W allowed), 0 <= shift < 8, C % heads == 0,
+ * B*H*W within an int, non-NULL buffers.  Head dims: ZS_BF16 8, 16, 24, 32 (MFMA kernel; with
+ * zs_tune_set("window_mfma", 0) only 24 and 32), ZS_F32 24 and 32; any other head dim returns
+ * ZS_ERR_UNSUPPORTED. */
 int zs_window_attention(const void* qkv, int B, int H, int W, int C, int heads, int ws, int shift,
                         const float* rel_table, void* out, int dtype, void* stream);
 
@@ -156,23 +167,32 @@ int zs_swin_block(float* x, int B, int H, int W, int C, int heads, int shift, co
                   const void* w2_packed, const float* b2, void* stream);
 
 /* zs_patch_merge_ln: htsat.py:492-511 gather x0..x3 of each 2x2 patch + LayerNorm(4C):
- * x [B][H][W][C] f32 -> y [B*(H/2)*(W/2)][4C] (dtype); the reduction Linear is a zs_gemm. */
+ * x [B][H][W][C] f32 -> y [B*(H/2)*(W/2)][4C] (dtype); the reduction Linear is a zs_gemm.
+ * Accepts B > 0, even H and W (H != W allowed), any C > 0, B*H*W within an int. */
 int zs_patch_merge_ln(const float* x, int B, int H, int W, int C, const float* ln_w,
                       const float* ln_b, void* y, int dtype, void* stream);
 
-/* zs_ln_meanpool: htsat.py:830,838-847 final LayerNorm + mean over the N tokens -> [B][C] f32. */
+/* zs_ln_meanpool: htsat.py:830,838-847 final LayerNorm + mean over the N tokens -> [B][C] f32.
+ * x [B][N][C] f32.  B, N > 0; 0 < C <= min(2048, L / 64) where L is the device's LDS limit per
+ * workgroup in bytes (hipDeviceAttributeMaxSharedMemoryPerBlock: the kernel keeps 16 x C f32
+ * partial sums in dynamic LDS).  gfx950 reports 160 KiB, so C <= 2048 there; a 64 KiB device
+ * accepts C <= 1024.  A larger C is refused with ZS_ERR_ARG, never launched. */
 int zs_ln_meanpool(const float* x, int B, int N, int C, const float* ln_w, const float* ln_b,
                    float* out, void* stream);
 
 /* ------------------------------------------------------------------ CNN14 (cnns.py:36-78,171-201)
  * zs_conv3x3_bn_relu: NHWC implicit-GEMM conv3x3 pad 1 (no bias) + eval BN + ReLU.
  *   x [B][H][W][Cin] (dtype), w [Cout][3][3][Cin] (dtype), bn folded as scale/shift f32 [Cout]
- *   (y = relu(conv*scale + shift)), out [B][H][W][Cout] (dtype). */
+ *   (y = relu(conv*scale + shift)), out [B][H][W][Cout] (dtype).
+ *   k = (ky*3 + kx)*Cin + ci.  Cin == 1 (w rows are the 9 taps zero-padded to 32: [Cout][32]) or
+ *   Cin % 32 == 0; any Cout > 0; B, H, W > 0 with B*H*W within an int; non-NULL buffers. */
 int zs_conv3x3_bn_relu(const void* x, int B, int H, int W, int Cin, const void* w, int Cout,
                        const float* scale, const float* shift, void* out, int dtype, void* stream);
-/* zs_avgpool2: 2x2 average pool (floor) NHWC, dtype in/out. */
+/* zs_avgpool2: 2x2 average pool (floor: an odd last row / column is dropped) NHWC, dtype in/out.
+ * B > 0, H >= 2, W >= 2, C > 0, B*H*W within an int; non-NULL buffers. */
 int zs_avgpool2(const void* x, int B, int H, int W, int C, void* out, int dtype, void* stream);
-/* zs_cnn_head: mean over freq (W) then max + mean over time (H): x [B][H][W][C] -> [B][C] f32. */
+/* zs_cnn_head: mean over freq (W) then max + mean over time (H): x [B][H][W][C] -> [B][C] f32.
+ * 0 < B <= 65535, H, W, C > 0, B*H*W within an int; non-NULL buffers. */
 int zs_cnn_head(const void* x, int B, int H, int W, int C, float* out, int dtype, void* stream);
 /* zs_cast: f32 -> dtype element copy (e.g. the bn0'd log-mel as the NHWC C=1 CNN14 input). */
 int zs_cast(const float* x, long n, void* y, int dtype, void* stream);

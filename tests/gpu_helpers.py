@@ -1,5 +1,6 @@
 """Device-buffer helpers shared by the kernel-by-kernel GPU tests (tests/test_gpu_glue.py,
-tests/test_gpu_magic_kernels.py)."""
+tests/test_gpu_magic_kernels.py, tests/test_gpu_mistral_kernels.py,
+tests/test_gpu_encoder_kernels.py)."""
 import torch
 
 

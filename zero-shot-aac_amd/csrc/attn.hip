@@ -993,6 +993,10 @@ extern "C" int zs_window_attention(const void* qkv, int B, int H, int W, int C, 
   ZS_REQUIRE(ws == 8 && H % ws == 0 && W % ws == 0, "zs_window_attention: ws must be 8 and divide H, W");
   ZS_REQUIRE(heads > 0 && C % heads == 0, "zs_window_attention: C %% heads");
   ZS_REQUIRE(shift >= 0 && shift < ws, "zs_window_attention: shift");
+  ZS_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "zs_window_attention: bad shape");
+  ZS_REQUIRE(qkv && rel_table && out, "zs_window_attention: NULL buffer");
+  ZS_REQUIRE((long)B * H * W <= 0x7fffffffL && (long)B * (H / ws) * (W / ws) * heads <= 0x7fffffffL,
+             "zs_window_attention: B*H*W (or windows x heads) does not fit an int");
   const int hd = C / heads;
   dim3 grid(B * (H / ws) * (W / ws), heads);
   hipStream_t st = S(stream);

@@ -141,7 +141,9 @@ extern "C" int zs_conv3x3_bn_relu(const void* x, int B, int H, int W, int Cin, c
                                   int Cout, const float* scale, const float* shift, void* out,
                                   int dtype, void* stream) {
   ZS_REQUIRE(B > 0 && H > 0 && W > 0 && Cout > 0, "zs_conv3x3: bad shape");
-  ZS_REQUIRE(Cin == 1 || Cin % BK == 0, "zs_conv3x3: Cin must be 1 or a multiple of 32");
+  ZS_REQUIRE(Cin == 1 || (Cin > 0 && Cin % BK == 0), "zs_conv3x3: Cin must be 1 or a multiple of 32");
+  ZS_REQUIRE(x && w && scale && shift && out, "zs_conv3x3: NULL buffer");
+  ZS_REQUIRE((long)B * H * W <= 0x7fffffffL, "zs_conv3x3: B*H*W does not fit an int");
   const int M = B * H * W;
   const int Kp = Cin == 1 ? BK : 9 * Cin;   // weights packed [Cout][Kp] (Cin==1: 9 taps + 0 pad)
   hipStream_t st = S(stream);
@@ -161,6 +163,8 @@ extern "C" int zs_conv3x3_bn_relu(const void* x, int B, int H, int W, int Cin, c
 extern "C" int zs_avgpool2(const void* x, int B, int H, int W, int C, void* out, int dtype,
                            void* stream) {
   ZS_REQUIRE(B > 0 && H >= 2 && W >= 2 && C > 0, "zs_avgpool2: bad shape");
+  ZS_REQUIRE(x && out, "zs_avgpool2: NULL buffer");
+  ZS_REQUIRE((long)B * H * W <= 0x7fffffffL, "zs_avgpool2: B*H*W does not fit an int");
   const long total = (long)B * (H / 2) * (W / 2) * C;
   if (dtype == ZS_BF16)
     hipLaunchKernelGGL(avgpool2_kernel<bf16_t>, dim3(cdiv(total, 256)), dim3(256), 0, S(stream),
@@ -175,6 +179,9 @@ extern "C" int zs_avgpool2(const void* x, int B, int H, int W, int C, void* out,
 extern "C" int zs_cnn_head(const void* x, int B, int H, int W, int C, float* out, int dtype,
                            void* stream) {
   ZS_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "zs_cnn_head: bad shape");
+  ZS_REQUIRE(x && out, "zs_cnn_head: NULL buffer");
+  ZS_REQUIRE((long)B * H * W <= 0x7fffffffL && B <= 65535,
+             "zs_cnn_head: B*H*W does not fit an int, or B > 65535 (grid.y)");
   dim3 grid(cdiv(C, 256), B);
   if (dtype == ZS_BF16)
     hipLaunchKernelGGL(cnn_head_kernel<bf16_t>, grid, dim3(256), 0, S(stream), (const bf16_t*)x, H,

@@ -550,6 +550,9 @@ extern "C" int zs_logmel(const float* wav, int B, int T, const float* window, co
                          const float* bn_mean, const float* bn_var, const float* bn_weight,
                          const float* bn_bias, float* out, void* stream) {
   ZS_REQUIRE(B > 0 && T > NFFT / 2, "zs_logmel: need T > 512 samples for reflect padding");
+  ZS_REQUIRE(wav && window && twiddle && melW && mel_lo && mel_hi && out, "zs_logmel: NULL buffer");
+  ZS_REQUIRE(!bn_mean || (bn_var && bn_weight && bn_bias), "zs_logmel: bn0 needs all four vectors");
+  ZS_REQUIRE((long)B * (T / HOP + 1) <= 0x7fffffffL, "zs_logmel: B * n_frames does not fit an int");
   const int n_frames = T / HOP + 1;
   const int total = B * n_frames;
   if (g_logmel_wave) {
@@ -570,7 +573,9 @@ extern "C" int zs_logmel(const float* wav, int B, int T, const float* window, co
 }
 
 extern "C" int zs_wav2img(const float* in, int B, int T_in, float* img, void* stream) {
-  ZS_REQUIRE(B > 0 && T_in > 1 && T_in <= 1024, "zs_wav2img: 1 < T_in <= 1024");
+  ZS_REQUIRE(B > 0 && T_in > 1 && T_in <= 1024, "zs_wav2img: B > 0, 1 < T_in <= 1024");
+  ZS_REQUIRE(in && img, "zs_wav2img: NULL buffer");
+  ZS_REQUIRE(B <= 0x7fffffff / 65536, "zs_wav2img: B * 65536 does not fit an int");
   const long total = (long)B * 65536;
   hipLaunchKernelGGL(wav2img_kernel, dim3(cdiv(total, 256)), dim3(256), 0, S(stream), in, T_in, img);
   ZS_LAUNCH_CHECK();
@@ -579,7 +584,8 @@ extern "C" int zs_wav2img(const float* in, int B, int T_in, float* img, void* st
 
 extern "C" int zs_patch_embed(const float* img, int B, const float* w, const float* b,
                               const float* ln_w, const float* ln_b, float* x, void* stream) {
-  ZS_REQUIRE(B > 0, "zs_patch_embed: B");
+  ZS_REQUIRE(B > 0 && B <= 0x7fffffff / 65536, "zs_patch_embed: B > 0, B * 65536 fits an int");
+  ZS_REQUIRE(img && w && b && ln_w && ln_b && x, "zs_patch_embed: NULL buffer");
   const long ntok = (long)B * 4096;
   hipLaunchKernelGGL(patch_embed_kernel, dim3(cdiv(ntok, 64)), dim3(256), 0, S(stream), img, w, b,
                      ln_w, ln_b, x, ntok);

@@ -234,10 +234,12 @@ extern "C" int zs_layernorm(const float* x, int M, int C, int ldx, const int* ro
                             void* stream) {
   ZS_REQUIRE(M >= 0 && C > 0 && ldx >= C && ldy >= C, "zs_layernorm: bad shape");
   if (M == 0) return 0;
+  ZS_REQUIRE(x && w && b && y, "zs_layernorm: NULL buffer");
   dim3 grid(cdiv(M, 4));
   const int yal = ydtype == ZS_BF16 ? 8 : 16;
+  // the register kernel reads x, w and b as float4 and stores 4 outputs at once
   if (C % 4 == 0 && ldx % 4 == 0 && C <= 1024 && ldy % 4 == 0 && ((uintptr_t)x & 15) == 0 &&
-      ((uintptr_t)y & (yal - 1)) == 0) {
+      ((uintptr_t)w & 15) == 0 && ((uintptr_t)b & 15) == 0 && ((uintptr_t)y & (yal - 1)) == 0) {
     const int nv = cdiv(C / 4, 64);
 #define LNR(TO, NV_)                                                                           \
   hipLaunchKernelGGL((layernorm_reg_kernel<TO, NV_>), grid, dim3(256), 0, S(stream), x, M, C,    \
@@ -262,7 +264,11 @@ extern "C" int zs_layernorm(const float* x, int M, int C, int ldx, const int* ro
 
 extern "C" int zs_patch_merge_ln(const float* x, int B, int H, int W, int C, const float* ln_w,
                                  const float* ln_b, void* y, int dtype, void* stream) {
-  ZS_REQUIRE(B > 0 && H % 2 == 0 && W % 2 == 0 && C > 0, "zs_patch_merge_ln: bad shape");
+  ZS_REQUIRE(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0,
+             "zs_patch_merge_ln: bad shape");
+  ZS_REQUIRE(x && ln_w && ln_b && y, "zs_patch_merge_ln: NULL buffer");
+  ZS_REQUIRE((long)B * H * W <= 0x7fffffffL && 4L * C <= 0x7fffffffL,
+             "zs_patch_merge_ln: B*H*W or 4C does not fit an int");
   const long ntok = (long)B * (H / 2) * (W / 2);
   const int C4 = 4 * C;
   if (C4 <= 64 * 24) {
@@ -295,7 +301,15 @@ extern "C" int zs_patch_merge_ln(const float* x, int B, int H, int W, int C, con
 extern "C" int zs_ln_meanpool(const float* x, int B, int N, int C, const float* ln_w,
                               const float* ln_b, float* out, void* stream) {
   ZS_REQUIRE(B > 0 && N > 0 && C > 0 && C <= 2048, "zs_ln_meanpool: bad shape (C <= 2048)");
-  const size_t smem = 16 * C * sizeof(float);
+  ZS_REQUIRE(x && ln_w && ln_b && out, "zs_ln_meanpool: NULL buffer");
+  // 16 waves x C partial sums of dynamic LDS: the device's per-workgroup limit (64 C bytes: 160 KiB
+  // on gfx950 admits every C <= 2048; a 64 KiB device stops at C = 1024)
+  const size_t smem = 16 * (size_t)C * sizeof(float);
+  int dev = 0, lds_max = 0;
+  ZS_CHECK_HIP(hipGetDevice(&dev));
+  ZS_CHECK_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  ZS_REQUIRE(smem <= (size_t)lds_max, "zs_ln_meanpool: C = %d needs %zu bytes of LDS, the device "
+             "allows %d per workgroup", C, smem, lds_max);
 #define LMP(CPL_)                                                                              \
   hipLaunchKernelGGL(ln_meanpool_kernel<CPL_>, dim3(B), dim3(1024), smem, S(stream), x, N, C,   \
                      ln_w, ln_b, out)
