@@ -472,6 +472,50 @@ int zs_lmhead_nblk(int V);
 int zs_argmax_finalize(const float* part_val, const int* part_idx, int M, int nblk, int* idx,
                        void* stream);
 
+/* ------------------------------------------------------------------ teacher-forced scoring
+ * log p(caption | clip): the cross-entropy the reference trains on (train_prompt.py:133, over
+ * ClapCaption_prompt.forward's logits, caption_model.py:297-313), on the sequence generate2 /
+ * generate_beam condition on (predict_prompt.py:129-148), temperature 1.
+ *
+ * zs_gpt2_score_embed: zs_gpt2_prefill_embed's scoring twin.  Clip b, H_b = hard_len[b],
+ * n = n_soft, T_b = cap_len[b], cap = cap_ids [B][Tmax]:
+ *   row b of x [B][Smax][D] = [wte(hard[b][:H_b]) ; soft[b] ; wte(cap[b][:T_b-1])] + wpe, zeros
+ *   from S_b = H_b + n + max(T_b - 1, 0) on;  plen[b] = S_b;
+ *   score_rows [B][Tmax] = b*Smax + H_b + n - 1 + t  (the row that predicts cap[b][t]) for
+ *   t < T_b, b*Smax beyond;  tgt [B][Tmax] = cap[b][t] for t < T_b, -1 beyond.
+ * Smax >= h_cap + n_soft + Tmax - 1, n_soft >= 1.  Nothing is clamped silently: an id outside
+ * [0, V) is embedded as id 0 and, if a caption id, its target becomes -1; a length outside
+ * [0, h_cap] / [0, Tmax] is cut to it; the number of such ids and lengths is ADDED to status[0]
+ * (the caller zeroes it before and raises on a count). */
+int zs_gpt2_score_embed(const int* hard_ids, const int* hard_len, int h_cap, const float* soft,
+                        int soft_ld, int n_soft, const int* cap_ids, const int* cap_len, int Tmax,
+                        const void* wte, const void* wpe, int V, int B, int Smax, int D, float* x,
+                        int* plen, int* score_rows, int* tgt, int* status, int dtype,
+                        void* stream);
+
+/* zs_lmhead_nll: the LM head of scoring (lm_logits = hidden . wte^T, caption_model.py:297-313, then
+ * the cross-entropy of train_prompt.py:133), fused: per row m of A [M][K] against W [V][K] and per
+ * column block of 128, the block's max and sum(exp(logit - max)) (part_stat [M][nblk][2], the
+ * layout and arithmetic of zs_lmhead_topk) and its top-1 (part_val / part_idx [M][nblk], ties ->
+ * lower index); and tgt_logit[m] = logit[m][tgt[m]], written by the one block that holds that
+ * column (no atomics).  A row with tgt[m] outside [0, V) writes no target logit.  No top-k list
+ * and no [M][V] logits are written.  K % 32 == 0, lda % 8 == 0, A and W 16-byte aligned. */
+int zs_lmhead_nll(int M, int K, int V, int dtype, const void* A, int lda, const void* W,
+                  const int* tgt, float* part_stat, float* part_val, int* part_idx,
+                  float* tgt_logit, void* stream);
+
+/* zs_nll_finalize: merges zs_lmhead_nll's partials, M = B x Tmax rows (caption b's rows are
+ * b*Tmax .. b*Tmax + Tmax - 1).  Per row: lse = log sum exp(logit), argmax[m] (lower index on
+ * ties), logprob[m] = tgt_logit[m] - lse -- log_softmax(logits)[target], the summand of the
+ * cross-entropy (train_prompt.py:133) -- or 0 for a row whose tgt is outside [0, V).  Per
+ * caption: sum[b] = its rows' logprob added in position order, cnt[b] = its rows with a target.
+ * lse may be NULL.  Every reduction runs in a fixed order: results are bit-identical from run to
+ * run. */
+int zs_nll_finalize(const float* part_stat, const float* part_val, const int* part_idx,
+                    const int* tgt, const float* tgt_logit, int M, int nblk, int V, int B,
+                    int Tmax, float* logprob, float* lse, int* argmax, float* sum, int* cnt,
+                    void* stream);
+
 /* zs_prefix_ids_assemble: get_prefix_tokens (gpt2_prefix_eval.py:271-278) with the argmax run
  * only over the soft-prompt rows: out[b][p] = hard_ids[b][p] for p < hard_len[b] (a hard row is
  * wte[id] and its own cosine is the maximum — the caller verifies that every possible hard id

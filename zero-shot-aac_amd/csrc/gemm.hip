@@ -1148,6 +1148,131 @@ __global__ __launch_bounds__(256) void lmhead_kernel(int xcd_order, int M, int K
   }
 }
 
+// ------------------------------------------------------------------ LM head, teacher-forced
+// Scoring a GIVEN token per row (cross-entropy over the caption tokens: train_prompt.py:133,
+// caption_model.py:297-313): lmhead_kernel's main loops and block order with another register
+// epilogue.  Per (row, 128-column block): the block's max, sum(exp(logit - max)) and top-1
+// (value, index; ties -> lower index) as lmhead_kernel writes them, and -- from the one lane of
+// the one block that holds column tgt[m] -- the target's logit into tgt_logit[m]: one writer per
+// row, no atomics.  No top-k list, no [M][V] logits.  Rows with tgt outside [0, V) write no
+// target logit.  The statistics use lmhead_kernel's arithmetic (__expf, the same merge order), so
+// the log-sum-exp of a row equals the one zs_lmhead_topk's partials give, bit for bit.
+template <typename T, int BM>
+__global__ __launch_bounds__(256) void lmhead_nll_kernel(int xcd_order, int M, int K, int V,
+                                                         const T* A, int lda, const T* W,
+                                                         const int* __restrict__ tgt,
+                                                         float* __restrict__ part_stat,
+                                                         float* __restrict__ part_val,
+                                                         int* __restrict__ part_idx,
+                                                         float* __restrict__ tgt_logit) {
+  constexpr int SM_LOOP = 2 * FastTile<BM, LM_BN>::STAGE;   // 4 waves (2x2), 2 stages
+  static_assert(2 * BM * 3 * 4 <= SM_LOOP, "epilogue exchange fits the ring's LDS");
+  __shared__ __attribute__((aligned(16))) char smem_raw[SM_LOOP];
+  // XCD-local block order: see lmhead_kernel
+  const int ntm = cdiv(M, BM), nblk = cdiv(V, LM_BN), nwg = nblk * ntm;
+  int vb, mb;
+  if (xcd_order & 1) {
+    const int b = blockIdx.x, x = b & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const int u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (b >> 3);
+    vb = u / ntm;
+    mb = u - vb * ntm;
+  } else {
+    vb = blockIdx.x % nblk;
+    mb = blockIdx.x / nblk;
+  }
+  const int n0 = vb * LM_BN, m0 = mb * BM;
+  // transposed product (vocab on the MFMA row axis), as lmhead_kernel's ring paths
+  f32x16_t acct[LM_BN / 64][BM / 64];
+  if constexpr (sizeof(T) == 4) {
+    const DenseRows ra{(const bf16_t*)A, 2 * lda, M, m0};
+    const DenseRows rw{(const bf16_t*)W, 2 * K, V, n0};
+    fast_mainloop<LM_BN, BM, 2, 2, 2, 64, false, 0, true>(rw, ra, 0, 2 * K, smem_raw, acct);
+  } else if (K % 64 == 0) {
+    if (xcd_order & 2)
+      lean_mainloop<LM_BN, BM, 2, 2, 2, 64, false, true>((const bf16_t*)W, K, V, n0,
+                                                         (const bf16_t*)A, lda, M, m0, K,
+                                                         smem_raw, acct);
+    else
+      lean_mainloop<LM_BN, BM, 2, 2, 2, 64>((const bf16_t*)W, K, V, n0, (const bf16_t*)A, lda, M,
+                                            m0, K, smem_raw, acct);
+  } else {
+    const DenseRows ra{(const bf16_t*)A, lda, M, m0};
+    const DenseRows rw{(const bf16_t*)W, K, V, n0};
+    fast_mainloop<LM_BN, BM>(rw, ra, 0, K, smem_raw, acct);
+  }
+  __syncthreads();
+  // acct[i][j][e]: vocab n0 + wr0 + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5), token
+  // m0 + wc0 + j*32 + (lane&31): a token's 64 logits of this wave sit in one lane pair
+  constexpr int TMV = LM_BN / 64, TNT = BM / 64;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr0 = (wid >> 1) * (LM_BN / 2), wc0 = (wid & 1) * (BM / 2), wg = wid >> 1;
+  float* xm = reinterpret_cast<float*>(smem_raw);          // [2][BM] max
+  float* xs = xm + 2 * BM;                                  // [2][BM] sum-exp
+  int* xi = reinterpret_cast<int*>(xs + 2 * BM);            // [2][BM] argmax
+#pragma unroll
+  for (int j = 0; j < TNT; ++j) {
+    const int r = wc0 + j * 32 + (lane & 31);                // token within the block
+    const int m = m0 + r;
+    const int t = m < M ? tgt[m] : -1;
+    float bv = -INFINITY, tl = 0.f;
+    int bi = 0x7fffffff;
+    bool hit = false;
+#pragma unroll
+    for (int i = 0; i < TMV; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+        const float cv = n < V ? acct[i][j][e] : -INFINITY;
+        const bool c = cv > bv;        // n increases with (i, e): strict > keeps the lower index
+        bv = c ? cv : bv;
+        bi = c ? n : bi;
+        const bool h = n == t && n < V;
+        tl = h ? acct[i][j][e] : tl;
+        hit = hit || h;
+      }
+    if (hit) tgt_logit[m] = tl;        // t >= 0 here, so m < M
+    {
+      const float pv = __shfl_xor(bv, 32, 64);
+      const int pi = __shfl_xor(bi, 32, 64);
+      const bool c = pv > bv || (pv == bv && pi < bi);
+      bv = c ? pv : bv;
+      bi = c ? pi : bi;
+    }
+    float se = 0.f;
+    if (bv != -INFINITY) {
+#pragma unroll
+      for (int i = 0; i < TMV; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+          if (n < V) se += __expf(acct[i][j][e] - bv);
+        }
+      se += __shfl_xor(se, 32, 64);
+    }
+    if (lane < 32) {
+      xm[wg * BM + r] = bv;
+      xs[wg * BM + r] = se;
+      xi[wg * BM + r] = bi;
+    }
+  }
+  __syncthreads();
+  // the two wave rows hold vocab halves [0, 64) and [64, 128) of the block: merge
+  for (int r = threadIdx.x; r < BM; r += 256) {
+    const int m = m0 + r;
+    if (m >= M) continue;
+    const float m0v = xm[r], m1v = xm[BM + r];
+    const float g = fmaxf(m0v, m1v);
+    const float se = (m0v == -INFINITY ? 0.f : xs[r] * expf(m0v - g)) +
+                     (m1v == -INFINITY ? 0.f : xs[BM + r] * expf(m1v - g));
+    const long o = (long)m * nblk + vb;
+    part_stat[o * 2 + 0] = g;
+    part_stat[o * 2 + 1] = se;
+    const bool hi = m1v > m0v;         // equal: the lower half's (lower) index
+    part_val[o] = hi ? m1v : m0v;
+    part_idx[o] = hi ? xi[BM + r] : xi[r];
+  }
+}
+
 }  // namespace zs
 
 using namespace zs;
@@ -1259,6 +1384,34 @@ extern "C" int zs_lmhead_topk_t(int M, int K, int V, int dtype, const void* A, i
   }
 #undef LMH_K
 #undef LMH
+  ZS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int zs_lmhead_nll(int M, int K, int V, int dtype, const void* A, int lda,
+                             const void* W, const int* tgt, float* part_stat, float* part_val,
+                             int* part_idx, float* tgt_logit, void* stream) {
+  ZS_REQUIRE(M > 0 && K > 0 && V > 0, "zs_lmhead_nll: bad shape");
+  ZS_REQUIRE(K % BK == 0 && lda % 8 == 0 && lda >= K, "zs_lmhead_nll: K %% 32, lda %% 8, lda >= K");
+  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_lmhead_nll: dtype");
+  ZS_REQUIRE(A && W && tgt && part_stat && part_val && part_idx && tgt_logit,
+             "zs_lmhead_nll: null pointer");
+  ZS_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
+             "zs_lmhead_nll: A and W must be 16-byte aligned");
+  hipStream_t st = S(stream);
+  const int nblk = cdiv(V, LM_BN);
+  const int order = (g_fast_xcd ? 1 : 0) | (g_lm_prio ? 2 : 0);
+#define LMN(T, BM_)                                                                            \
+  hipLaunchKernelGGL((lmhead_nll_kernel<T, BM_>), dim3(nblk * cdiv(M, BM_)), dim3(256), 0, st, \
+                     order, M, K, V, (const T*)A, lda, (const T*)W, tgt, part_stat, part_val,  \
+                     part_idx, tgt_logit)
+  // the row tiles of zs_lmhead_topk: 64 rows up to M = 64, 128 above
+  if (M <= 64) {
+    if (dtype == ZS_BF16) LMN(bf16_t, 64); else LMN(float, 64);
+  } else {
+    if (dtype == ZS_BF16) LMN(bf16_t, 128); else LMN(float, 128);
+  }
+#undef LMN
   ZS_LAUNCH_CHECK();
   return 0;
 }

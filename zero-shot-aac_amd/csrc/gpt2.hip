@@ -5,6 +5,9 @@
 //  * embed_tokens     — decode-step input embedding;
 //  * argmax_finalize / greedy_step / beam_step — generate2 / generate_beam bookkeeping on device
 //    (gpt2_prefix_eval.py:99-158, 161-222) so a captured decode step needs no host round trip.
+//  * score_embed / nll_rows / nll_caption — teacher-forced scoring of a given caption
+//    (train_prompt.py:133 on the sequence of predict_prompt.py:129-148): the scored sequence's
+//    embedding, and the merge of zs_lmhead_nll's partials into per-token and per-caption log-probs.
 #include "common.h"
 
 namespace zs {
@@ -524,6 +527,116 @@ __global__ void beam_advance_kernel(const int* __restrict__ stopped, int R, int*
   }
 }
 
+// ------------------------------------------------------------------ teacher-forced scoring
+// prefill_embed's scoring twin: row b is [wte(hard) ; soft ; wte(cap[:T-1])] (+ wpe), S rows.
+// Block (0, b) also writes the clip's bookkeeping and counts what it had to correct: an id
+// outside [0, V) (embedded as id 0, its target -1) and a length outside its buffer (clamped).
+template <typename T>
+__global__ void score_embed_kernel(const int* __restrict__ hard_ids,
+                                   const int* __restrict__ hard_len, int h_cap,
+                                   const float* __restrict__ soft, int soft_ld, int n_soft,
+                                   const int* __restrict__ cap_ids,
+                                   const int* __restrict__ cap_len, int Tmax,
+                                   const T* __restrict__ wte, const T* __restrict__ wpe, int V,
+                                   int Smax, int D, float* __restrict__ x, int* __restrict__ plen,
+                                   int* __restrict__ score_rows, int* __restrict__ tgt,
+                                   int* __restrict__ status) {
+  const int b = blockIdx.y, p = blockIdx.x;
+  const int Hr = hard_len[b], Tr = cap_len[b];
+  const int H = min(max(Hr, 0), h_cap), Tc = min(max(Tr, 0), Tmax);
+  const int P = H + n_soft, S = P + max(Tc - 1, 0);
+  if (p == 0) {
+    int bad = 0;
+    if (threadIdx.x == 0) {
+      plen[b] = S;
+      bad += (Hr != H) + (Tr != Tc);
+    }
+    for (int t = threadIdx.x; t < Tmax; t += blockDim.x) {
+      int row = b * Smax, id = -1;
+      if (t < Tc) {
+        row = b * Smax + P - 1 + t;
+        id = cap_ids[(long)b * Tmax + t];
+        if (id < 0 || id >= V) { id = -1; ++bad; }
+      }
+      score_rows[(long)b * Tmax + t] = row;
+      tgt[(long)b * Tmax + t] = id;
+    }
+    for (int h = threadIdx.x; h < H; h += blockDim.x) {
+      const int id = hard_ids[(long)b * h_cap + h];
+      bad += id < 0 || id >= V;
+    }
+    if (bad) atomicAdd(status, bad);
+  }
+  int id = -1;                                   // < 0: not a token row
+  if (p < H) id = hard_ids[(long)b * h_cap + p];
+  else if (p >= P && p < S) id = cap_ids[(long)b * Tmax + p - P];
+  const bool tok = p < H || (p >= P && p < S);
+  if (tok && (id < 0 || id >= V)) id = 0;
+  const long o = ((long)b * Smax + p) * D;
+  for (int d = threadIdx.x; d < D; d += blockDim.x) {
+    float xv = 0.f;
+    if (p < S) {
+      const float e = tok ? ldf(wte + (long)id * D + d)
+                          : soft[(long)b * soft_ld + (long)(p - H) * D + d];
+      xv = e + ldf(wpe + (long)p * D + d);
+    }
+    x[o + d] = xv;
+  }
+}
+
+// one wave per LM-head row: lse over the row's nblk (max, sum-exp) partials -- each lane its
+// blocks lane, lane + 64, .. in increasing order, then the fixed xor butterfly, as beam_step_kernel
+// merges them -- the row's argmax, and logprob = tgt_logit - lse (0 for a row without a target)
+__global__ __launch_bounds__(256) void nll_rows_kernel(
+    const float* __restrict__ pstat, const float* __restrict__ pv, const int* __restrict__ pi,
+    const int* __restrict__ tgt, const float* __restrict__ tgt_logit, int M, int nblk, int V,
+    float* __restrict__ logprob, float* __restrict__ lse, int* __restrict__ amax) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= M) return;
+  float mx = -INFINITY;
+  for (int k = lane; k < nblk; k += 64) mx = fmaxf(mx, pstat[((long)r * nblk + k) * 2]);
+  mx = wave_max(mx);
+  float s = 0.f;
+  for (int k = lane; k < nblk; k += 64) {
+    const float bm = pstat[((long)r * nblk + k) * 2];
+    s += pstat[((long)r * nblk + k) * 2 + 1] * expf(bm - mx);
+  }
+  s = wave_sum(s);
+  const int a = row_argmax(pv, pi, r, nblk, lane);
+  if (lane == 0) {
+    const float l = mx + logf(s);
+    const int t = tgt[r];
+    logprob[r] = (t >= 0 && t < V) ? tgt_logit[r] - l : 0.f;
+    if (lse) lse[r] = l;
+    amax[r] = a;
+  }
+}
+
+// one wave per caption: its Tmax row log-probs summed in position order (every lane adds the
+// same values in the same order), the rows with a target counted
+__global__ __launch_bounds__(64) void nll_caption_kernel(const float* __restrict__ logprob,
+                                                          const int* __restrict__ tgt, int Tmax,
+                                                          int V, float* __restrict__ sum,
+                                                          int* __restrict__ cnt) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float s = 0.f;
+  int n = 0;
+  for (int c = 0; c < Tmax; c += 64) {
+    const int t = c + lane;
+    const int id = t < Tmax ? tgt[(long)b * Tmax + t] : -1;
+    const bool ok = id >= 0 && id < V;
+    const float v = ok ? logprob[(long)b * Tmax + t] : 0.f;
+    n += __popcll(__ballot(ok));
+    const int q1 = min(64, Tmax - c);
+    for (int q = 0; q < q1; ++q) s += __shfl(v, q, 64);
+  }
+  if (lane == 0) {
+    sum[b] = s;
+    cnt[b] = n;
+  }
+}
+
 }  // namespace zs
 
 using namespace zs;
@@ -716,6 +829,56 @@ extern "C" int zs_beam_step(const float* part_stat, const float* part_val, const
   ZS_LAUNCH_CHECK();
   hipLaunchKernelGGL(beam_advance_kernel, dim3(1), dim3(1024), 0, S(stream), stopped, C * beam,
                      step_ctr, max_steps, all_done);
+  ZS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int zs_gpt2_score_embed(const int* hard_ids, const int* hard_len, int h_cap,
+                                   const float* soft, int soft_ld, int n_soft, const int* cap_ids,
+                                   const int* cap_len, int Tmax, const void* wte, const void* wpe,
+                                   int V, int B, int Smax, int D, float* x, int* plen,
+                                   int* score_rows, int* tgt, int* status, int dtype,
+                                   void* stream) {
+  ZS_REQUIRE(B > 0 && D > 0 && V > 0 && Tmax > 0 && h_cap >= 0 && n_soft >= 1 && soft_ld >= 0,
+             "zs_gpt2_score_embed: bad shape");
+  ZS_REQUIRE((long)h_cap + n_soft + Tmax - 1 <= Smax,
+             "zs_gpt2_score_embed: Smax %d < h_cap + n_soft + Tmax - 1", Smax);
+  ZS_REQUIRE(B <= 65535 && (long)B * Smax < (1L << 31), "zs_gpt2_score_embed: B x Smax too large");
+  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_gpt2_score_embed: dtype");
+  ZS_REQUIRE(hard_len && soft && cap_ids && cap_len && wte && wpe && x && plen && score_rows &&
+                 tgt && status && (hard_ids || h_cap == 0),
+             "zs_gpt2_score_embed: null pointer");
+  dim3 grid(Smax, B);
+  if (dtype == ZS_BF16)
+    hipLaunchKernelGGL(score_embed_kernel<bf16_t>, grid, dim3(256), 0, S(stream), hard_ids,
+                       hard_len, h_cap, soft, soft_ld, n_soft, cap_ids, cap_len, Tmax,
+                       (const bf16_t*)wte, (const bf16_t*)wpe, V, Smax, D, x, plen, score_rows, tgt,
+                       status);
+  else
+    hipLaunchKernelGGL(score_embed_kernel<float>, grid, dim3(256), 0, S(stream), hard_ids,
+                       hard_len, h_cap, soft, soft_ld, n_soft, cap_ids, cap_len, Tmax,
+                       (const float*)wte, (const float*)wpe, V, Smax, D, x, plen, score_rows, tgt,
+                       status);
+  ZS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int zs_nll_finalize(const float* part_stat, const float* part_val, const int* part_idx,
+                               const int* tgt, const float* tgt_logit, int M, int nblk, int V,
+                               int B, int Tmax, float* logprob, float* lse, int* argmax,
+                               float* sum, int* cnt, void* stream) {
+  ZS_REQUIRE(M > 0 && nblk > 0 && B > 0 && Tmax > 0 && (long)B * Tmax == M,
+             "zs_nll_finalize: bad shape (M = B x Tmax)");
+  // (a one-token vocabulary has nothing to score)
+  ZS_REQUIRE(V > 1 && nblk == cdiv(V, 128), "zs_nll_finalize: V > 1, nblk = ceil(V / 128)");
+  ZS_REQUIRE(part_stat && part_val && part_idx && tgt && tgt_logit && logprob && argmax && sum &&
+                 cnt,
+             "zs_nll_finalize: null pointer");
+  hipLaunchKernelGGL(nll_rows_kernel, dim3(cdiv(M, 4)), dim3(256), 0, S(stream), part_stat,
+                     part_val, part_idx, tgt, tgt_logit, M, nblk, V, logprob, lse, argmax);
+  ZS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(nll_caption_kernel, dim3(B), dim3(64), 0, S(stream), logprob, tgt, Tmax, V,
+                     sum, cnt);
   ZS_LAUNCH_CHECK();
   return 0;
 }

@@ -71,6 +71,9 @@ SIGNATURES = {
     "zs_lmhead_topk_t": [I, I, I, I, P, I, P, I, I, F, P, P, P, P],
     "zs_lmhead_nblk": [I],
     "zs_argmax_finalize": [P, P, I, I, P, P],
+    "zs_gpt2_score_embed": [P, P, I, P, I, I, P, P, I, P, P, I, I, I, I, P, P, P, P, P, I, P],
+    "zs_lmhead_nll": [I, I, I, I, P, I, P, P, P, P, P, P, P],
+    "zs_nll_finalize": [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P],
     "zs_prefix_ids_assemble": [P, I, P, P, I, I, I, P, P],
     "zs_greedy_step": [P, P, I, I, P, I, I, I, P, P, P, P, P, P, P],
     "zs_greedy_init": [I, P, P, P, P, P, I, P, P, P],

@@ -426,6 +426,59 @@ def argmax_finalize(part_val, part_idx, M, nblk, idx):
     return idx
 
 
+# ---------------------------------------------------------------- teacher-forced scoring
+def score_embed(hard_ids, hard_len, soft, soft_ld, n_soft, cap_ids, cap_len, wte, wpe, B, Smax, x,
+                plen, score_rows, tgt, status):
+    """zs_gpt2_score_embed: the scored sequences of B clips into x [B*Smax, D] (+ plen,
+    score_rows / tgt [B, Tmax]); bad ids and lengths are counted into status[0]."""
+    for t, n in ((hard_ids, "hard_ids"), (hard_len, "hard_len"), (cap_ids, "cap_ids"),
+                 (cap_len, "cap_len"), (plen, "plen"), (score_rows, "score_rows"), (tgt, "tgt"),
+                 (status, "status")):
+        _i32(t, n)
+    V, D = wte.shape
+    Tmax, h_cap = cap_ids.shape[1], hard_ids.shape[1]
+    _need(soft.dtype == torch.float32 and x.dtype == torch.float32, "score_embed: soft / x f32")
+    _need(cap_ids.is_contiguous() and hard_ids.is_contiguous(), "score_embed: contiguous ids")
+    _need(hard_ids.shape[0] >= B and hard_len.numel() >= B and cap_ids.shape[0] >= B
+          and cap_len.numel() >= B and plen.numel() >= B and x.numel() >= B * Smax * D
+          and score_rows.numel() >= B * Tmax and tgt.numel() >= B * Tmax
+          and wpe.shape[0] >= Smax and wpe.dtype == wte.dtype, "score_embed: buffer sizes")
+    call("zs_gpt2_score_embed", _p(hard_ids), _p(hard_len), h_cap, _p(soft), soft_ld, n_soft,
+         _p(cap_ids), _p(cap_len), Tmax, _p(wte), _p(wpe), V, B, Smax, D, _p(x), _p(plen),
+         _p(score_rows), _p(tgt), _p(status), dt(wte), _s())
+
+
+def lmhead_nll(a, w, tgt, part_stat, part_val, part_idx, tgt_logit, M=None):
+    """zs_lmhead_nll: per-block softmax statistics and top-1 of a [M, K] . w [V, K]^T and the
+    logit of column tgt[m] of every row, without writing the logits."""
+    K = a.shape[-1]
+    M = M if M is not None else a.numel() // K
+    V, nblk = w.shape[0], lmhead_nblk(w.shape[0])
+    _i32(tgt, "tgt"), _i32(part_idx, "part_idx")
+    _need(a.dtype == w.dtype and w.shape[1] == K, "lmhead_nll: dtype/shape mismatch")
+    _need(tgt.numel() >= M and tgt_logit.numel() >= M and part_stat.numel() >= 2 * M * nblk
+          and part_val.numel() >= M * nblk and part_idx.numel() >= M * nblk
+          and part_stat.dtype == part_val.dtype == tgt_logit.dtype == torch.float32,
+          "lmhead_nll: buffer sizes")
+    call("zs_lmhead_nll", M, K, V, dt(a), _p(a), a.stride(-2) if a.dim() > 1 else K, _p(w),
+         _p(tgt), _p(part_stat), _p(part_val), _p(part_idx), _p(tgt_logit), _s())
+
+
+def nll_finalize(part_stat, part_val, part_idx, tgt, tgt_logit, V, B, Tmax, logprob, argmax, sum,
+                 cnt, lse=None):
+    """zs_nll_finalize: lmhead_nll's partials of B x Tmax rows -> per-row logprob / argmax
+    (/ lse) and per-caption sum / cnt."""
+    M, nblk = B * Tmax, lmhead_nblk(V)
+    _i32(tgt, "tgt"), _i32(part_idx, "part_idx"), _i32(argmax, "argmax"), _i32(cnt, "cnt")
+    _need(tgt.numel() >= M and tgt_logit.numel() >= M and logprob.numel() >= M
+          and argmax.numel() >= M and (lse is None or lse.numel() >= M) and sum.numel() >= B
+          and cnt.numel() >= B and part_stat.numel() >= 2 * M * nblk
+          and part_val.numel() >= M * nblk and part_idx.numel() >= M * nblk
+          and logprob.dtype == sum.dtype == torch.float32, "nll_finalize: buffer sizes")
+    call("zs_nll_finalize", _p(part_stat), _p(part_val), _p(part_idx), _p(tgt), _p(tgt_logit), M,
+         nblk, V, B, Tmax, _p(logprob), _p(lse), _p(argmax), _p(sum), _p(cnt), _s())
+
+
 def prefix_ids_assemble(hard_ids, hard_len, soft_idx, n_soft, B, Pmax, out):
     _i32(hard_ids, "hard_ids"), _i32(hard_len, "hard_len"), _i32(soft_idx, "soft_idx"), _i32(out, "out")
     call("zs_prefix_ids_assemble", _p(hard_ids), hard_ids.shape[-1], _p(hard_len), _p(soft_idx),

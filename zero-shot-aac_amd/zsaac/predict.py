@@ -17,7 +17,9 @@ modes on the hot path (greedy ``generate2`` and ``generate_beam(beam_size=3)``):
 The tokenizer is GPT-2 byte-level BPE from a local ``vocab.json`` + ``merges.txt``
 (``--tokenizer``; ``zsaac.bpe``).  ``--magic`` (predict_prompt.py:121-140) runs CLAP-guided
 beam decoding, ``generate_beam_magic(beam_size=3, magic_width, alpha 0.1, beta 0.2)`` with
-``audio_embeds = prefix``, batched on zsaac.magic.MagicDecoder; the CLAP checkpoint
+``audio_embeds = prefix``, batched on zsaac.magic.MagicDecoder; ``--score`` writes no captions
+but ``nll.txt``, the teacher-forced NLL of the pickle's reference captions (zsaac.score); the CLAP
+checkpoint
 (``--clap``, the reference's HTSAT-BERT-ZS.pt: ``{"model": ASE state dict}``) supplies the BERT
 text tower and ``--bert_vocab`` its WordPiece vocabulary (bert-base-uncased's vocab.txt).
 """
@@ -182,6 +184,49 @@ def make_preds_magic(pipe: CaptionPipeline, tokenizer, all_data: List[Dict], cla
     return key2pred, key2pred_prefix, key2refs
 
 
+def reference_ids(tokenizer, caption, max_tokens: int) -> List[int]:
+    """A reference caption as the training set tokenises it (dataset/dataset.py:337-346): '.'
+    appended when missing, whole-string BPE, cut to the sequence limit."""
+    c = caption["caption"] if isinstance(caption, dict) else str(caption)
+    if not c or c[-1] != ".":
+        c = c + "."
+    return list(tokenizer.encode(c))[:max_tokens]
+
+
+def score_refs(pipe: CaptionPipeline, tokenizer, all_data: List[Dict], max_tokens: int = 67):
+    """``--score``: every clip's reference captions teacher-forced through the model
+    (zsaac.score.CaptionScorer), ``pipe.cfg.batch`` (clip, reference) pairs per call.  Returns
+    ({audio_id: (sum NLL, tokens, references)}, corpus perplexity)."""
+    from .score import CaptionScorer, CaptionScores
+    scorer = CaptionScorer(pipe, max_tokens)
+    pairs = [(i, reference_ids(tokenizer, c, max_tokens))
+             for i, it in enumerate(all_data) for c in it.get("caption", [])]
+    B, parts = pipe.cfg.batch, []
+    for c0 in range(0, len(pairs), B):
+        chunk = pairs[c0:c0 + B]
+        emb = safeload.stack_rows([all_data[i]["audio_embedding"] for i, _ in chunk]).to(pipe.dev)
+        parts.append(scorer.score_emb(emb, [ids for _, ids in chunk]))
+    per_clip = {it["audio_id"]: [0.0, 0, 0] for it in all_data}
+    if not parts:
+        return per_clip, float("nan")
+    res = CaptionScores.cat(parts).cpu()
+    for (i, _), s, n in zip(pairs, res.sum_logprob.tolist(), res.n_tokens.tolist()):
+        acc = per_clip[all_data[i]["audio_id"]]
+        acc[0] -= s
+        acc[1] += n
+        acc[2] += 1
+    return per_clip, res.perplexity()
+
+
+def write_nll(test_dir: str, per_clip, perplexity: float) -> None:
+    """nll.txt: per clip ``audio_id <tab> mean NLL per token over its references <tab> tokens
+    <tab> references``, then the corpus perplexity exp(total NLL / total tokens)."""
+    with open(os.path.join(test_dir, "nll.txt"), "w") as f:
+        for k, (nll, n, r) in per_clip.items():
+            f.write("{}\t{:.6f}\t{}\t{}\n".format(k, nll / n if n else float("nan"), n, r))
+        f.write("perplexity: {:.6f}\n".format(perplexity))
+
+
 def write_outputs(test_dir: str, key2pred, key2pred_prefix, key2refs) -> Optional[Dict]:
     """output.txt exactly as predict_prompt.py:172-181; scores.txt (:155-170) when the
     captioning metrics are importable."""
@@ -237,6 +282,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--clap", type=str, default=None,
                     help="--magic: CLAP checkpoint ({'model': ASE state dict}, predict_prompt.py:125)")
     ap.add_argument("--bert_vocab", type=str, default=None, help="--magic: BERT vocab.txt")
+    ap.add_argument("--score", action="store_true",
+                    help="score the pickle's reference captions instead of generating: nll.txt")
     args = ap.parse_args(argv)
     if args.magic and not (args.clap and args.bert_vocab):
         raise SystemExit("--magic needs --clap <checkpoint> and --bert_vocab <vocab.txt>")
@@ -246,6 +293,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     pipe, _ = build_pipeline(args.test_dir, params, tokenizer, args.isbeam, dtype, args.batch,
                              args.device)
     all_data = safeload.load_pickle(args.test_data)
+    if args.score:
+        write_nll(args.test_dir, *score_refs(pipe, tokenizer, all_data))
+        return 0
     if args.magic:
         from transformers import BertTokenizer
         ck = torch.load(args.clap, map_location="cpu", weights_only=True)
