@@ -101,10 +101,22 @@ int zs_layernorm(const float* x, int M, int C, int ldx, const int* rows, const f
 /* zs_gemm: out[m][n] = act(sum_k A[m][k] * W[n][k] + bias[n]) + residual[m][n]
  *   A [M][lda], W [N][ldw] in `dtype`; bias f32 or NULL; residual f32 [M][ldr] or NULL (may alias
  *   out); out in `out_dtype`.  K % 32 == 0.  split_k > 1 needs a f32 workspace of
- *   split_k*M*N floats (deterministic slab reduction, no atomics).  split_k == 0 = auto: for
- *   M <= 64 (decode) a weight-streaming split-K kernel whose last-arriving workgroup reduces the
- *   slabs in order (deterministic); it needs a workspace of zs_gemm_workspace_floats(M,N,K) floats
- *   ZEROED ONCE at allocation (its tile counters re-arm themselves).
+ *   split_k*M*N floats (deterministic slab reduction, no atomics; its contents on entry do not
+ *   matter).  split_k == 0 = auto: bf16 M <= 64 takes the row-group kernel (no workspace) at the
+ *   K it covers (256, 512, 768, 1024, 1536, 2048, 3072, 3840, 4096); otherwise, for M <= 64 (and
+ *   up to 256 rows for f32, or bf16 with K >= 2048 on a small grid) and K % 64 == 0, a
+ *   weight-streaming split-K kernel whose last-arriving workgroup reduces the slabs in order
+ *   (deterministic); it needs a workspace of zs_gemm_workspace_floats(M,N,K) floats
+ *   ZEROED ONCE at allocation (its tile counters re-arm themselves); without one, the tiled kernel.
+ *   Accepts: M >= 0 (M == 0: nothing is done), any N > 0; lda >= K and ldw >= K, both multiples of
+ *   8 ELEMENTS, A and W 16-byte aligned; only columns [0, K) of rows [0, M) / [0, N) are read, so
+ *   padding columns and rows behind them may hold anything, NaN included.  ldo >= N, ldr >= N and
+ *   the alignment of out, residual and bias are free: 16-byte aligned bases with ldo % 8 == 0
+ *   (ldr % 4 == 0) take vector stores (loads), everything else the scalar paths, with the same
+ *   result; only columns [0, N) of rows [0, M) of out are written.
+ *   Refuses (ZS_ERR_ARG, nothing launched): M < 0, N <= 0, K <= 0, K % 32 != 0, lda or ldw not a
+ *   multiple of 8 or smaller than K, A or W not 16-byte aligned, split_k < 0, split_k > 1 without
+ *   a workspace, a dtype other than ZS_F32 / ZS_BF16.
  *   Replaces every nn.Linear / HF Conv1D on the path (Conv1D weights are repacked to [N][K]). */
 int zs_gemm(int M, int N, int K, int dtype, const void* A, int lda, const void* W, int ldw,
             const float* bias, const float* residual, int ldr, void* out, int ldo, int out_dtype,
@@ -115,20 +127,27 @@ int zs_gemm_workspace_floats(int M, int N, int K);
 /* zs_gemm_ln: out[m][n] = act(sum_k LN(x[m])[k] * W[n][k] + bias[n]) + residual[m][n] for
  *   M <= 64 rows (the GPT-2 decode step at the reference's eval batch of 64): LayerNorm over K
  *   (eps; ln_w / ln_b f32) of the f32 rows x [M][ldx], rounded to bf16, times bf16 W [N][ldw].
+ *   ln_w == ln_b == NULL: normalise only (the caller folded the affine into W and bias).
  *   Replaces the ln_1 -> attn.c_attn and ln_2 -> mlp.c_fc launch pairs of transformers'
- *   GPT2Block (the zs_layernorm + zs_gemm sequence).  K % 128 == 0, K <= 1024; x, ln_w, ln_b
- *   and W 16-byte aligned.  One launch, no workspace. */
+ *   GPT2Block (the zs_layernorm + zs_gemm sequence).  One launch, no workspace.
+ *   Accepts: 1 <= M <= 64, K 768 or 1024, any N > 0; ldx % 4 == 0, ldw % 8 == 0, ldx >= K,
+ *   ldw >= K; x, ln_w, ln_b and W 16-byte aligned; only columns [0, K) of x and W are read.  ldo, ldr and the alignment
+ *   of out, residual and bias are free (as zs_gemm).  Everything else is refused before a launch. */
 int zs_gemm_ln(int M, int N, int K, const float* x, int ldx, const float* ln_w, const float* ln_b,
                float eps, const void* W, int ldw, const float* bias, const float* residual,
                int ldr, void* out, int ldo, int out_dtype, int act, void* stream);
 
 /* zs_gemm_ln_f32: zs_gemm_ln with f32 W [N][ldw] and f32 out (the f32 parity mode's decode
- *   step): LayerNorm of the f32 rows x with the affine (ln_w, ln_b) applied in f32, exact f32
- *   products and f32 accumulation (v_mfma_f32_16x16x4_f32).  M <= 64, K 768 or 1024; x, W and
- *   the LN params 16-byte aligned.  Replaces GPT2Block's ln_1 -> c_attn / ln_2 -> c_fc pairs.
- *   ln_w == ln_b == NULL: no LayerNorm (out = act(x W^T + b) + residual, K up to 3072: the
- *   attn.c_proj / mlp.c_proj of the same step).  zs_gemm keeps its own f32 kernels, so a row's
- *   zs_gemm result stays independent of how many rows share the launch. */
+ *   step): LayerNorm of the f32 rows x with the affine (ln_w, ln_b) applied in f32 (no rounding
+ *   of the normalised rows), exact f32 products and f32 accumulation (v_mfma_f32_16x16x4_f32).
+ *   1 <= M <= 64, K 768 or 1024; ldx % 4 == 0, ldw % 4 == 0, ldx >= K, ldw >= K; x, W and the
+ *   LN params 16-byte aligned (anything else is refused before a launch); ldo, ldr and the
+ *   alignment of out, residual and bias are free.  Replaces GPT2Block's
+ *   ln_1 -> c_attn / ln_2 -> c_fc pairs.
+ *   ln_w == ln_b == NULL: no LayerNorm at all (out = act(x W^T + b) + residual, K 768, 1024 or
+ *   3072: the attn.c_proj / mlp.c_proj of the same step); there is no normalise-only mode here.
+ *   zs_gemm keeps its own f32 kernels, so a row's zs_gemm result stays independent of how many
+ *   rows share the launch. */
 int zs_gemm_ln_f32(int M, int N, int K, const float* x, int ldx, const float* ln_w,
                    const float* ln_b, float eps, const float* W, int ldw, const float* bias,
                    const float* residual, int ldr, float* out, int ldo, int act, void* stream);
@@ -450,14 +469,19 @@ int zs_embed_tokens_map(const int* tok, const int* pos, const int* rowmap, int n
  * computing them, gpt2_prefix_eval.py:200-215; their outputs are discarded either way). */
 int zs_compact_rows(const int* done, int nrows, int* rowmap, int* n_active, void* stream);
 
-/* zs_lmhead_topk: per row m of A [M][K] (dtype) against W [V][K] (dtype; tied wte):
- *   logits = A W^T, split in column blocks of 128; per (row, block) writes the block's max,
- *   sum(exp(logit - max)) and its top-`topk` (value, index) (ties -> lower index).
+/* zs_lmhead_topk: per row m of A [M][lda] (dtype) against W [V][K] (dtype, contiguous rows; tied
+ *   wte): logits = A W^T, split in column blocks of 128; per (row, block) writes the block's max,
+ *   sum(exp(logit - max)) and its top-`topk` (value, index), ordered by value descending, then
+ *   index ascending (ties -> lower index, in the list and at its cut).
  *   part_stat [M][nblk][2] f32, part_val [M][nblk][topk] f32, part_idx [M][nblk][topk] int32,
- *   nblk = ceil(V/128).  topk <= 8.  part_stat may be NULL (argmax callers: greedy generate2,
- *   get_prefix_tokens): the max / sum-exp pass is then skipped.  With row_norm != 0 each A row
- *   is L2-normalised first
- *   (get_prefix_tokens, gpt2_prefix_eval.py:271-278: W must then be normalize(wte)). */
+ *   nblk = ceil(V/128); every (row, block) is written.  A last block with fewer than topk
+ *   columns fills its list with padding entries (value -inf, index 0x7fffffff).  1 <= topk <= 8.
+ *   part_stat may be NULL (argmax callers: greedy generate2, get_prefix_tokens): the max /
+ *   sum-exp pass is then skipped and nothing is written there.  With row_norm != 0 each A row is
+ *   L2-normalised first (logits / max(||a||, 1e-12))
+ *   (get_prefix_tokens, gpt2_prefix_eval.py:271-278: W must then be normalize(wte)).
+ *   Accepts: M, K, V > 0, K % 32 == 0, lda % 8 == 0 and lda >= K (padding columns are not read),
+ *   A and W 16-byte aligned, dtype ZS_F32 / ZS_BF16; everything else is refused before a launch. */
 int zs_lmhead_topk(int M, int K, int V, int dtype, const void* A, int lda, const void* W,
                    int topk, int row_norm, float* part_stat, float* part_val, int* part_idx,
                    void* stream);

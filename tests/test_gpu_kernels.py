@@ -680,8 +680,9 @@ def _decode_map_body(cuda):
 def test_lmhead_topk(cuda, dtype, M):
     from zsaac import ops
     K, V, k = 768, 50257, 5
-    a = torch.randn(M, K, device=cuda).to(dtype)
-    w = (torch.randn(V, K, device=cuda) * 0.05).to(dtype)
+    g = torch.Generator(device="cuda").manual_seed(50257 + M)
+    a = torch.randn(M, K, device=cuda, generator=g).to(dtype)
+    w = (torch.randn(V, K, device=cuda, generator=g) * 0.05).to(dtype)
     nblk = ops.lmhead_nblk(V)
     ps = torch.empty(M, nblk, 2, device=cuda)
     pv = torch.empty(M, nblk, k, device=cuda)

@@ -122,7 +122,12 @@ __device__ __forceinline__ float act_apply(float x, int act) {
 // GELU (erf form, nn.GELU default) with erf from Abramowitz & Stegun 7.1.26: one v_rcp, one v_exp
 // and a degree-5 polynomial, no branches (ocml's erff is a piecewise polynomial whose branches
 // diverge across a wave).  |gelu error| <= 2.2e-7 absolute over the whole line (checked against
-// scipy in float64), far below bf16 rounding; used only where the result is stored as bf16.
+// scipy in float64), far below bf16 rounding.  Used by every epi_slab epilogue (the lean tiles,
+// gemm_big_kernel and gemm_fast_kernel, bf16 and f32 operands, bf16 and f32 output) and by the
+// rows kernel's bf16 output; against the exact formula in float64 the f32-output cases of
+// tests/test_gpu_gemm_kernels.py stay within the f32 tolerance (erf GELU on the f32 ring:
+// 1.58e-06 at a float32 yardstick of 4.7e-07, tolerance 2.9e-06; the register-staged f32 kernel
+// with erff measures 1.63e-06 on its case: the accumulation, not the activation, sets both).
 __device__ __forceinline__ float gelu_erf_fast(float x) {
   const float z = fabsf(x) * 0.70710678118654752f;
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
@@ -134,9 +139,11 @@ __device__ __forceinline__ float gelu_erf_fast(float x) {
   return x * (x >= 0.f ? fmaf(-0.5f, q, 1.0f) : 0.5f * q);
 }
 
-// bf16-output epilogues: the same activations in cheaper forms whose error (a few f32 ulp) is far
-// below bf16 rounding.  gelu_new = x * sigmoid(2u) exactly (0.5 * (1 + tanh u) = sigmoid(2u)),
-// one v_exp_f32 + one reciprocal instead of tanhf; the f32 parity path keeps act_apply.
+// The tiled epilogues (epi_slab, any output type) and the rows kernel's bf16 output: the same
+// activations in cheaper forms whose error is a few f32 ulp.  gelu_new = x * sigmoid(2u) exactly
+// (0.5 * (1 + tanh u) = sigmoid(2u)), one v_exp_f32 + one reciprocal instead of tanhf.  The
+// register-staged gemm_kernel<T>, splitk_reduce_kernel, the skinny kernel, the rows kernels' f32
+// output and gemm_rows_f32_kernel (the f32 decode step) keep act_apply.
 __device__ __forceinline__ float act_apply_fast(float x, int act) {
   if (act == ACT_GELU_TANH) {
     const float u2 = -1.5957691216057308f * (x + 0.044715f * x * x * x);   // -2*sqrt(2/pi)*(...)

@@ -955,20 +955,25 @@ __global__ __launch_bounds__(256) void lmhead_kernel(int xcd_order, int M, int K
           float cv = n < V ? acct[i][j][e] * sc : -INFINITY;
           if (tdiv) cv = cv / temp;
           int ci = n;
-          // n increases with (i, e): strict > keeps the lower index first among equals.  The
-          // bubble insertion is select-only (per-element branches became ~500 divergent
-          // exec-mask branches per kernel); the outer test skips a value no lane keeps
+          // n increases with (i, e): a value goes behind its equals (strict >), so the lower
+          // index stays first.  The list is descending, hence lt[q] = cv > tv[q] is monotone in q
+          // and slot q takes cv where lt[q] && !lt[q - 1], its upper neighbour where both hold:
+          // every entry behind the new one moves down one slot whatever it compares to.  (The
+          // earlier bubble compared the DISPLACED entry with strict > against its successor, so
+          // among equals the lower index slid behind the higher one or fell off the list.)
+          // Select-only (per-element branches became ~500 divergent exec-mask branches per
+          // kernel), all compares on the old list; the outer test skips a value no lane keeps
           if (cv > tv[KMAX - 1]) {
+            bool lt[KMAX];
 #pragma unroll
-            for (int q = 0; q < KMAX; ++q) {
-              const bool c = cv > tv[q];
-              const float t = tv[q];
-              const int u = ti[q];
-              tv[q] = c ? cv : t;
-              ti[q] = c ? ci : u;
-              cv = c ? t : cv;
-              ci = c ? u : ci;
+            for (int q = 0; q < KMAX; ++q) lt[q] = cv > tv[q];
+#pragma unroll
+            for (int q = KMAX - 1; q >= 1; --q) {
+              tv[q] = lt[q] ? (lt[q - 1] ? tv[q - 1] : cv) : tv[q];
+              ti[q] = lt[q] ? (lt[q - 1] ? ti[q - 1] : ci) : ti[q];
             }
+            tv[0] = lt[0] ? cv : tv[0];
+            ti[0] = lt[0] ? ci : ti[0];
           }
         }
       // merge with the partner lane's list (both lanes end with the same top-KMAX)
@@ -1087,19 +1092,18 @@ __global__ __launch_bounds__(256) void lmhead_kernel(int xcd_order, int M, int K
     if (KMAX == 1) {
       if (v > tv[0]) { tv[0] = v; ti[0] = n; }
     } else if (v > tv[KMAX - 1]) {
-      // bubble the new value up the (static-indexed) list
-      float cv = v;
-      int ci = n;
+      // place the new value in the (static-indexed) descending list: select-only, as the
+      // transposed path above (lt[q] is monotone in q; entries behind the new one move down)
+      bool lt[KMAX];
 #pragma unroll
-      for (int q = 0; q < KMAX; ++q) {   // select-only, as the transposed path above
-        const bool c = cv > tv[q];
-        const float t = tv[q];
-        const int u = ti[q];
-        tv[q] = c ? cv : t;
-        ti[q] = c ? ci : u;
-        cv = c ? t : cv;
-        ci = c ? u : ci;
+      for (int q = 0; q < KMAX; ++q) lt[q] = v > tv[q];
+#pragma unroll
+      for (int q = KMAX - 1; q >= 1; --q) {
+        tv[q] = lt[q] ? (lt[q - 1] ? tv[q - 1] : v) : tv[q];
+        ti[q] = lt[q] ? (lt[q - 1] ? ti[q - 1] : n) : ti[q];
       }
+      tv[0] = lt[0] ? v : tv[0];
+      ti[0] = lt[0] ? n : ti[0];
     }
   }
   // combine max across the TPR threads of this row (consecutive lanes)
@@ -1293,6 +1297,7 @@ extern "C" int zs_gemm(int M, int N, int K, int dtype, const void* A, int lda, c
   ZS_REQUIRE(M >= 0 && N > 0 && K > 0, "zs_gemm: bad shape M=%d N=%d K=%d", M, N, K);
   ZS_REQUIRE(K % BK == 0, "zs_gemm: K=%d must be a multiple of 32", K);
   ZS_REQUIRE(lda % 8 == 0 && ldw % 8 == 0, "zs_gemm: lda/ldw must be multiples of 8");
+  ZS_REQUIRE(lda >= K && ldw >= K, "zs_gemm: lda=%d / ldw=%d smaller than K=%d", lda, ldw, K);
   // the tiled and skinny kernels load A and W rows with 16-byte LDS-DMA / vector loads
   ZS_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
              "zs_gemm: A and W must be 16-byte aligned");
@@ -1349,7 +1354,8 @@ extern "C" int zs_lmhead_topk_t(int M, int K, int V, int dtype, const void* A, i
   ZS_REQUIRE(temperature > 0.f, "zs_lmhead_topk_t: temperature %g (> 0)", temperature);
   ZS_REQUIRE(!row_norm || temperature == 1.0f, "zs_lmhead_topk_t: row_norm with temperature");
   ZS_REQUIRE(M > 0 && K > 0 && V > 0, "zs_lmhead_topk: bad shape");
-  ZS_REQUIRE(K % BK == 0 && lda % 8 == 0, "zs_lmhead_topk: K %% 32, lda %% 8");
+  ZS_REQUIRE(K % BK == 0 && lda % 8 == 0 && lda >= K, "zs_lmhead_topk: K %% 32, lda %% 8, lda >= K");
+  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_lmhead_topk: dtype");
   ZS_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
              "zs_lmhead_topk: A and W must be 16-byte aligned");
   ZS_REQUIRE(topk >= 1 && topk <= MAXK, "zs_lmhead_topk: 1 <= topk <= 8");

@@ -527,6 +527,7 @@ extern "C" int zs_gemm_ln(int M, int N, int K, const float* x, int ldx, const fl
   ZS_REQUIRE(ldx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)ln_w & 15) == 0 &&
              ((uintptr_t)ln_b & 15) == 0, "zs_gemm_ln: x / LN params must be 16-byte aligned");
   ZS_REQUIRE(ldw % 8 == 0 && ((uintptr_t)W & 15) == 0, "zs_gemm_ln: W must be 16-byte aligned");
+  ZS_REQUIRE(ldx >= K && ldw >= K, "zs_gemm_ln: ldx=%d / ldw=%d smaller than K=%d", ldx, ldw, K);
   ZS_REQUIRE(out_dtype == ZS_BF16 || out_dtype == ZS_F32, "zs_gemm_ln: out dtype");
   const RowsPlan p = rows_plan(N, K, true);
   ZS_REQUIRE(p.waves > 0, "zs_gemm_ln: unsupported K=%d (768 or 1024)", K);
@@ -549,6 +550,7 @@ extern "C" int zs_gemm_ln_f32(int M, int N, int K, const float* x, int ldx, cons
   ZS_REQUIRE(ldx % 4 == 0 && ldw % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)W & 15) == 0 &&
              ((uintptr_t)ln_w & 15) == 0 && ((uintptr_t)ln_b & 15) == 0,
              "zs_gemm_ln_f32: x / W / LN params must be 16-byte aligned, ldx / ldw multiples of 4");
+  ZS_REQUIRE(ldx >= K && ldw >= K, "zs_gemm_ln_f32: ldx=%d / ldw=%d smaller than K=%d", ldx, ldw, K);
   const bool ln = ln_w != nullptr;
   ZS_REQUIRE(ln ? (K == 768 || K == 1024) : (K == 768 || K == 1024 || K == 3072),
              "zs_gemm_ln_f32: unsupported K=%d (768 / 1024, or 3072 without LayerNorm)", K);
