@@ -540,6 +540,36 @@ int zs_nll_finalize(const float* part_stat, const float* part_val, const int* pa
                     int Tmax, float* logprob, float* lse, int* argmax, float* sum, int* cnt,
                     void* stream);
 
+/* ------------------------------------------------------------------ retrieval metrics
+ * zs_sim_rank: the rank of given gallery items, the quantity behind a2t / t2a
+ * (retrieval/tools/utils.py:169-251: `np.argsort(d)[::-1]` over a materialised similarity row,
+ * then `np.where(inds == i)`), fused.  Queries Q [M][ldq], gallery G [N][ldg] (dtype),
+ * sim[m][n] = Q[m] . G[n] accumulated in f32; targets tgt [M][T] int32, 1 <= T <= 8.  For every
+ * (m, t) with j = tgt[m][t] in [0, N):
+ *   tgt_sim[m][t] = sim[m][j]
+ *   rank[m][t]    = #{n != j : sim[m][n] > sim[m][j]} + #{n < j : sim[m][n] == sim[m][j]}
+ * -- the 0-based position of j in the row sorted by value descending, then index ascending.  A
+ * target outside [0, N) gives rank -1 and tgt_sim 0; two targets of a row may name one column.
+ * No [M][N] matrix and no per-block partials exist anywhere: the kernel runs twice (first the
+ * blocks that hold a target store its similarity, then every block counts), so the target's value
+ * and the values compared with it come from the same MFMA chain and exact duplicates tie; counts
+ * are integer atomics on rank (zeroed here, on `stream`), hence independent of the block order
+ * and bit-identical from run to run.
+ * Accepts: M, N, K > 0, K % 32 == 0, ldq / ldg % 8 == 0 and >= K (padding columns are not read),
+ * Q and G 16-byte aligned, no NULL pointer, M x T < 2^31; everything else is refused before any
+ * launch with the outputs untouched. */
+int zs_sim_rank(int M, int N, int K, int dtype, const void* Q, int ldq, const void* G, int ldg,
+                const int* tgt, int T, float* tgt_sim, int* rank, void* stream);
+
+/* zs_sim_topk_finalize: nearest neighbours (`cosine_similarity(...).topk(5)`,
+ * data_handing/embeddings_related_generator.py:19-28; `audio_emb @ text_embeds.t()` then the best
+ * class, retrieval/zero_shot_classification.py:82-106): merges the [M][nblk][kpart] partial lists
+ * zs_lmhead_topk writes (W = the gallery) into the row's global top-k, out_val / out_idx [M][k],
+ * value descending, then index ascending; padding entries (-inf, 0x7fffffff) come last.
+ * 1 <= k <= kpart <= 8.  One wave per row, fixed order. */
+int zs_sim_topk_finalize(const float* part_val, const int* part_idx, int M, int nblk, int kpart,
+                         int k, float* out_val, int* out_idx, void* stream);
+
 /* zs_prefix_ids_assemble: get_prefix_tokens (gpt2_prefix_eval.py:271-278) with the argmax run
  * only over the soft-prompt rows: out[b][p] = hard_ids[b][p] for p < hard_len[b] (a hard row is
  * wte[id] and its own cosine is the maximum — the caller verifies that every possible hard id

@@ -1277,6 +1277,177 @@ __global__ __launch_bounds__(256) void lmhead_nll_kernel(int xcd_order, int M, i
   }
 }
 
+// ------------------------------------------------------------------ similarity rank (retrieval)
+// Retrieval metrics (a2t / t2a, retrieval/tools/utils.py:169-251) need, per query row m and target
+// column j = tgt[m][t], the position of j in the row sorted by similarity: rank = #{n : sim[m][n] >
+// sim[m][j]} + #{n < j : sim[m][n] == sim[m][j]} (value descending, then index ascending).
+// lmhead_nll_kernel's main loops, block order and tiles with another register epilogue, launched
+// twice so that every compared value -- the target's own included -- comes out of the same MFMA
+// chain (an exact duplicate of the target row then compares EQUAL, whatever the rounding):
+//   PASS 0  only the blocks whose 128 columns hold a target of one of their rows run the main
+//           loop; the one lane that holds column tgt[m][t] writes tgt_sim[m][t] (one writer per
+//           slot up to equal targets, which write the same bits).
+//   PASS 1  every block counts, per (row, t), its columns that sort before the target; the lane
+//           pair and the two wave rows are summed in registers / LDS and ONE integer atomicAdd per
+//           (row, t, block) with a non-zero count goes to rank[m][t].  Integer sums commute: the
+//           result does not depend on the order of the blocks.  No [M][N] matrix, no partials.
+// Targets outside [0, N) count nothing (sim_rank_init_kernel has set their rank to -1).
+__global__ void sim_rank_init_kernel(long total, int N, const int* __restrict__ tgt,
+                                     float* __restrict__ tgt_sim, int* __restrict__ rank) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int j = tgt[i];
+  const bool ok = j >= 0 && j < N;
+  rank[i] = ok ? 0 : -1;
+  if (!ok) tgt_sim[i] = 0.f;
+}
+
+template <typename T, int BM, int PASS>
+__global__ __launch_bounds__(256) void sim_rank_kernel(int xcd_order, int M, int K, int N,
+                                                       const T* Q, int ldq, const T* G, int ldg,
+                                                       const int* __restrict__ tgt, int TT,
+                                                       float* __restrict__ tgt_sim,
+                                                       int* __restrict__ rank) {
+  constexpr int SM_LOOP = 2 * FastTile<BM, LM_BN>::STAGE;   // 4 waves (2x2), 2 stages
+  static_assert(BM * MAXK * 4 <= SM_LOOP, "epilogue exchange fits the ring's LDS");
+  __shared__ __attribute__((aligned(16))) char smem_raw[SM_LOOP];
+  // XCD-local block order: see lmhead_kernel
+  const int ntm = cdiv(M, BM), nblk = cdiv(N, LM_BN), nwg = nblk * ntm;
+  int vb, mb;
+  if (xcd_order & 1) {
+    const int b = blockIdx.x, x = b & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const int u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (b >> 3);
+    vb = u / ntm;
+    mb = u - vb * ntm;
+  } else {
+    vb = blockIdx.x % nblk;
+    mb = blockIdx.x / nblk;
+  }
+  const int n0 = vb * LM_BN, m0 = mb * BM;
+  if constexpr (PASS == 0) {
+    // a block none of whose rows has a target in its columns has nothing to store
+    // (the vote goes through the ring's own LDS: ONE __shared__ array, as lmhead_kernel)
+    int* flag = reinterpret_cast<int*>(smem_raw);
+    if (threadIdx.x == 0) *flag = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < BM * TT; i += 256) {
+      const int m = m0 + i / TT;
+      if (m < M) {
+        const int j = tgt[(long)m0 * TT + i];
+        if (j >= n0 && j < n0 + LM_BN && j < N) *flag = 1;
+      }
+    }
+    __syncthreads();
+    const int any = *flag;
+    __syncthreads();                                   // read before the main loop's DMA lands
+    if (!any) return;
+  }
+  // transposed product (gallery on the MFMA row axis), as lmhead_nll_kernel
+  f32x16_t acct[LM_BN / 64][BM / 64];
+  if constexpr (sizeof(T) == 4) {
+    const DenseRows ra{(const bf16_t*)Q, 2 * ldq, M, m0};
+    const DenseRows rw{(const bf16_t*)G, 2 * ldg, N, n0};
+    fast_mainloop<LM_BN, BM, 2, 2, 2, 64, false, 0, true>(rw, ra, 0, 2 * K, smem_raw, acct);
+  } else if (K % 64 == 0) {
+    if (xcd_order & 2)
+      lean_mainloop<LM_BN, BM, 2, 2, 2, 64, false, true>((const bf16_t*)G, ldg, N, n0,
+                                                         (const bf16_t*)Q, ldq, M, m0, K,
+                                                         smem_raw, acct);
+    else
+      lean_mainloop<LM_BN, BM, 2, 2, 2, 64>((const bf16_t*)G, ldg, N, n0, (const bf16_t*)Q, ldq, M,
+                                            m0, K, smem_raw, acct);
+  } else {
+    const DenseRows ra{(const bf16_t*)Q, ldq, M, m0};
+    const DenseRows rw{(const bf16_t*)G, ldg, N, n0};
+    fast_mainloop<LM_BN, BM>(rw, ra, 0, K, smem_raw, acct);
+  }
+  __syncthreads();
+  // acct[i][j][e]: column n0 + wr0 + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5), query
+  // m0 + wc0 + j*32 + (lane&31): a query's 64 similarities of this wave sit in one lane pair
+  constexpr int TMV = LM_BN / 64, TNT = BM / 64;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr0 = (wid >> 1) * (LM_BN / 2), wc0 = (wid & 1) * (BM / 2), wg = wid >> 1;
+  int* xc = reinterpret_cast<int*>(smem_raw);               // [BM][MAXK] counts of wave row 1
+  int cnt[TNT][MAXK];
+#pragma unroll
+  for (int j = 0; j < TNT; ++j) {
+    const int r = wc0 + j * 32 + (lane & 31);                // query within the block
+    const int m = m0 + r;
+    int tj[MAXK];
+    float ts[MAXK];
+#pragma unroll
+    for (int t = 0; t < MAXK; ++t) {
+      cnt[j][t] = 0;
+      tj[t] = -1;
+      ts[t] = INFINITY;
+      if (t < TT && m < M) {
+        const int c = tgt[(long)m * TT + t];
+        if (c >= 0 && c < N) {
+          tj[t] = c;
+          if constexpr (PASS == 1) ts[t] = tgt_sim[(long)m * TT + t];
+        }
+      }
+    }
+    if constexpr (PASS == 0) {
+#pragma unroll
+      for (int t = 0; t < MAXK; ++t) {
+        if (t >= TT) break;                                  // uniform
+        // which accumulator element of THIS lane holds column tj, if any: invert
+        // n = n0 + wr0 + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5)
+        const int rel = tj[t] - n0 - wr0;                    // tj < N, so a hit is a real column
+        const bool mine = tj[t] >= 0 && rel >= 0 && rel < LM_BN / 2 && ((rel >> 2) & 1) == (lane >> 5);
+        const int slot = mine ? (rel >> 5) * 16 + (rel & 3) + 4 * ((rel & 31) >> 3) : -1;
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < TMV; ++i)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) v = slot == i * 16 + e ? acct[i][j][e] : v;
+        if (mine) tgt_sim[(long)m * TT + t] = v;             // tj >= 0 here, so m < M
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < MAXK; ++t) {
+        if (t >= TT) break;                                  // uniform
+        int c = 0;
+#pragma unroll
+        for (int i = 0; i < TMV; ++i)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+            const float cv = acct[i][j][e];
+            // before the target: a greater value, or an equal one at a lower index (n == tj
+            // itself is neither); padding columns n >= N are not counted
+            c += (n < N && (cv > ts[t] || (cv == ts[t] && n < tj[t]))) ? 1 : 0;
+          }
+        cnt[j][t] = c + __shfl_xor(c, 32, 64);
+      }
+    }
+  }
+  if constexpr (PASS == 1) {
+    // the two wave rows hold column halves [0, 64) and [64, 128) of the block: add, then one
+    // integer atomic per (query, t) of this block
+    if (wg == 1 && lane < 32) {
+#pragma unroll
+      for (int j = 0; j < TNT; ++j)
+#pragma unroll
+        for (int t = 0; t < MAXK; ++t) xc[(wc0 + j * 32 + lane) * MAXK + t] = cnt[j][t];
+    }
+    __syncthreads();
+    if (wg == 0 && lane < 32) {
+#pragma unroll
+      for (int j = 0; j < TNT; ++j) {
+        const int r = wc0 + j * 32 + lane;
+        const int m = m0 + r;
+#pragma unroll
+        for (int t = 0; t < MAXK; ++t) {
+          const int c = cnt[j][t] + xc[r * MAXK + t];
+          if (t < TT && m < M && c != 0) atomicAdd(rank + (long)m * TT + t, c);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace zs
 
 using namespace zs;
@@ -1418,6 +1589,48 @@ extern "C" int zs_lmhead_nll(int M, int K, int V, int dtype, const void* A, int 
     if (dtype == ZS_BF16) LMN(bf16_t, 128); else LMN(float, 128);
   }
 #undef LMN
+  ZS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int zs_sim_rank(int M, int N, int K, int dtype, const void* Q, int ldq, const void* G,
+                           int ldg, const int* tgt, int T, float* tgt_sim, int* rank,
+                           void* stream) {
+  ZS_REQUIRE(M > 0 && N > 0 && K > 0, "zs_sim_rank: bad shape");
+  ZS_REQUIRE(K % BK == 0 && ldq % 8 == 0 && ldg % 8 == 0 && ldq >= K && ldg >= K,
+             "zs_sim_rank: K %% 32, ldq / ldg %% 8 and >= K");
+  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_sim_rank: dtype");
+  ZS_REQUIRE(T >= 1 && T <= MAXK, "zs_sim_rank: 1 <= T <= 8");
+  ZS_REQUIRE(Q && G && tgt && tgt_sim && rank, "zs_sim_rank: null pointer");
+  ZS_REQUIRE(((uintptr_t)Q & 15) == 0 && ((uintptr_t)G & 15) == 0,
+             "zs_sim_rank: Q and G must be 16-byte aligned");
+  const long total = (long)M * T;
+  const int nblk = cdiv(N, LM_BN);
+  // M x T and the 1-D grid of the 64-row tile must fit an int
+  ZS_REQUIRE(total < (1L << 31) && (long)nblk * cdiv(M, 64) < (1L << 31),
+             "zs_sim_rank: M x T or the grid does not fit an int");
+  hipStream_t st = S(stream);
+  const int order = (g_fast_xcd ? 1 : 0) | (g_lm_prio ? 2 : 0);
+  hipLaunchKernelGGL(sim_rank_init_kernel, dim3((unsigned)cdiv(total, 256L)), dim3(256), 0, st,
+                     total, N, tgt, tgt_sim, rank);
+  ZS_LAUNCH_CHECK();
+#define SRK(T_, BM_, P_)                                                                        \
+  hipLaunchKernelGGL((sim_rank_kernel<T_, BM_, P_>), dim3(nblk * cdiv(M, BM_)), dim3(256), 0, st, \
+                     order, M, K, N, (const T_*)Q, ldq, (const T_*)G, ldg, tgt, T, tgt_sim, rank)
+#define SRK2(T_, BM_)                                                                           \
+  do {                                                                                          \
+    SRK(T_, BM_, 0);                                                                            \
+    ZS_LAUNCH_CHECK();                                                                          \
+    SRK(T_, BM_, 1);                                                                            \
+  } while (0)
+  // the row tiles of zs_lmhead_nll: 64 rows up to M = 64, 128 above
+  if (M <= 64) {
+    if (dtype == ZS_BF16) SRK2(bf16_t, 64); else SRK2(float, 64);
+  } else {
+    if (dtype == ZS_BF16) SRK2(bf16_t, 128); else SRK2(float, 128);
+  }
+#undef SRK2
+#undef SRK
   ZS_LAUNCH_CHECK();
   return 0;
 }

@@ -278,6 +278,42 @@ __global__ void argmax_finalize_kernel(const float* __restrict__ pv, const int* 
   if (lane == 0) idx[r] = t;
 }
 
+// Nearest neighbours (cosine_similarity(...).topk(5), embeddings_related_generator.py:19-28;
+// audio_emb @ text_embeds.t() then argmax / topk, zero_shot_classification.py:82-106): the row's
+// global top-k out of zs_lmhead_topk's [nblk][kpart] partial lists, value descending, then index
+// ascending.  One wave per row; pick q is the best entry strictly behind pick q - 1 in that order
+// (row_argmax's compare), so every pick is one fixed-order wave reduction and no entry is marked.
+// A column sits in one list only, so real entries are distinct; padding entries (-inf,
+// 0x7fffffff) are the last element of the order and fill whatever is left.
+__global__ void sim_topk_finalize_kernel(const float* __restrict__ pv, const int* __restrict__ pi,
+                                         int M, int nblk, int kpart, int k,
+                                         float* __restrict__ out_val, int* __restrict__ out_idx) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (r >= M) return;
+  const long base = (long)r * nblk * kpart;
+  const int n = nblk * kpart;
+  float lv = INFINITY;       // the previous pick: everything is behind (+inf, -1)
+  int li = -1;
+  for (int q = 0; q < k; ++q) {
+    float v = -INFINITY;
+    int i = 0x7fffffff;
+    for (int e = lane; e < n; e += 64) {
+      const float cv = pv[base + e];
+      const int ci = pi[base + e];
+      const bool behind = cv < lv || (cv == lv && ci > li);
+      if (behind && (cv > v || (cv == v && ci < i))) { v = cv; i = ci; }
+    }
+    wave_argmax(v, i);
+    if (lane == 0) {
+      out_val[(long)r * k + q] = v;
+      out_idx[(long)r * k + q] = i;
+    }
+    lv = v;
+    li = i;
+  }
+}
+
 // one wave per row, 4 rows per block.  The blocks combine "rows still alive" and their arrival
 // in ONE relaxed agent-scope atomic on all_done[1] (arrivals in the low 16 bits, alive rows in
 // the high 16): the block that draws the last ticket knows every block has read *step_ctr and
@@ -745,6 +781,19 @@ extern "C" int zs_argmax_finalize(const float* part_val, const int* part_idx, in
   ZS_REQUIRE(M > 0 && nblk > 0, "zs_argmax_finalize: bad shape");
   hipLaunchKernelGGL(argmax_finalize_kernel, dim3(cdiv(M, 4)), dim3(256), 0, S(stream), part_val,
                      part_idx, M, nblk, idx);
+  ZS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int zs_sim_topk_finalize(const float* part_val, const int* part_idx, int M, int nblk,
+                                    int kpart, int k, float* out_val, int* out_idx,
+                                    void* stream) {
+  ZS_REQUIRE(M > 0 && nblk > 0, "zs_sim_topk_finalize: bad shape");
+  ZS_REQUIRE(k >= 1 && k <= kpart && kpart <= 8, "zs_sim_topk_finalize: 1 <= k <= kpart <= 8");
+  ZS_REQUIRE((long)nblk * kpart < (1L << 31), "zs_sim_topk_finalize: nblk x kpart too large");
+  ZS_REQUIRE(part_val && part_idx && out_val && out_idx, "zs_sim_topk_finalize: null pointer");
+  hipLaunchKernelGGL(sim_topk_finalize_kernel, dim3(cdiv(M, 4)), dim3(256), 0, S(stream),
+                     part_val, part_idx, M, nblk, kpart, k, out_val, out_idx);
   ZS_LAUNCH_CHECK();
   return 0;
 }

@@ -74,6 +74,8 @@ SIGNATURES = {
     "zs_gpt2_score_embed": [P, P, I, P, I, I, P, P, I, P, P, I, I, I, I, P, P, P, P, P, I, P],
     "zs_lmhead_nll": [I, I, I, I, P, I, P, P, P, P, P, P, P],
     "zs_nll_finalize": [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P],
+    "zs_sim_rank": [I, I, I, I, P, I, P, I, P, I, P, P, P],
+    "zs_sim_topk_finalize": [P, P, I, I, I, I, P, P, P],
     "zs_prefix_ids_assemble": [P, I, P, P, I, I, I, P, P],
     "zs_greedy_step": [P, P, I, I, P, I, I, I, P, P, P, P, P, P, P],
     "zs_greedy_init": [I, P, P, P, P, P, I, P, P, P],

@@ -479,6 +479,36 @@ def nll_finalize(part_stat, part_val, part_idx, tgt, tgt_logit, V, B, Tmax, logp
          nblk, V, B, Tmax, _p(logprob), _p(lse), _p(argmax), _p(sum), _p(cnt), _s())
 
 
+# ---------------------------------------------------------------- retrieval metrics
+def sim_rank(q, g, tgt, tgt_sim, rank, M=None):
+    """zs_sim_rank: rank[m][t] / tgt_sim[m][t] of gallery item tgt[m][t] in q [M, K] . g [N, K]^T
+    (value descending, then index ascending), without writing the similarities."""
+    K = q.shape[-1]
+    M = M if M is not None else q.shape[0]
+    _i32(tgt, "tgt"), _i32(rank, "rank")
+    _need(q.dim() == 2 and g.dim() == 2 and tgt.dim() == 2, "sim_rank: q, g, tgt are 2-D")
+    T = tgt.shape[1]
+    _need(q.dtype == g.dtype and g.shape[1] == K and q.stride(1) == 1 and g.stride(1) == 1,
+          "sim_rank: dtype/shape mismatch")
+    _need(tgt.is_contiguous() and tgt_sim.is_contiguous() and rank.is_contiguous()
+          and q.shape[0] >= M and tgt.shape[0] >= M and tgt_sim.numel() >= M * T
+          and rank.numel() >= M * T and tgt_sim.dtype == torch.float32, "sim_rank: buffer sizes")
+    call("zs_sim_rank", M, g.shape[0], K, dt(q), _p(q), q.stride(0), _p(g), g.stride(0), _p(tgt),
+         T, _p(tgt_sim), _p(rank), _s())
+
+
+def sim_topk_finalize(part_val, part_idx, M, nblk, kpart, k, out_val, out_idx):
+    """zs_sim_topk_finalize: zs_lmhead_topk's [M, nblk, kpart] partial lists -> the row's top-k."""
+    _i32(part_idx, "part_idx"), _i32(out_idx, "out_idx")
+    _need(part_val.numel() >= M * nblk * kpart and part_idx.numel() >= M * nblk * kpart
+          and out_val.numel() >= M * k and out_idx.numel() >= M * k
+          and part_val.dtype == out_val.dtype == torch.float32
+          and part_val.is_contiguous() and part_idx.is_contiguous()
+          and out_val.is_contiguous() and out_idx.is_contiguous(), "sim_topk_finalize: buffers")
+    call("zs_sim_topk_finalize", _p(part_val), _p(part_idx), M, nblk, kpart, k, _p(out_val),
+         _p(out_idx), _s())
+
+
 def prefix_ids_assemble(hard_ids, hard_len, soft_idx, n_soft, B, Pmax, out):
     _i32(hard_ids, "hard_ids"), _i32(hard_len, "hard_len"), _i32(soft_idx, "soft_idx"), _i32(out, "out")
     call("zs_prefix_ids_assemble", _p(hard_ids), hard_ids.shape[-1], _p(hard_len), _p(soft_idx),
