@@ -329,6 +329,36 @@ def test_begin_groups_ragged_batches(cuda):
     assert runner.gave_up == 0
 
 
+def test_staged_schedule_reuses_pipelines(cuda):
+    """The staged schedule with fewer pipelines than batches: 86 embeddings in batches of 16 (the
+    last 6) through two pipelines and two grids of 48 at a time, so each pipeline takes three
+    batches -- its next begin ordered after the last batch's result copy, which ran on the
+    grid's stream.  Ids and prompt lengths equal a single-stream run's over three repetitions."""
+    from tools import idparity
+    from zsaac.pipeline import ConcurrentRunner
+    g = idparity.load("c2_gpt2init")
+    base = torch.from_numpy(g["clap_emb"]).to(cuda)
+    n = 86
+    i = torch.arange(n, device=cuda, dtype=torch.float32)[:, None]
+    emb = base[torch.arange(n, device=cuda) % base.shape[0]] * (1.0 + 0.05 * torch.sin(0.37 * i))
+    batches = [emb[a:a + 16] for a in range(0, n, 16)]
+    assert [int(b.shape[0]) for b in batches] == [16] * 5 + [6]
+    p = _pipe(g, cuda, True, batch=16)
+    p.decoder.persist_grid = 48
+    single = [(p.caption_emb(b).captions(), p.result().plen.tolist()) for b in batches]
+    runner = ConcurrentRunner(p, 2, begin_first=True, grids=[48], budget=96)
+    assert runner.begin_first and len(runner.pipes) == 2
+    runner.warmup_emb(batches[0])
+    for rep in range(3):
+        outs = runner.run(batches, inputs="emb")
+        for k, o in enumerate(outs):
+            assert o.captions() == single[k][0], f"repetition {rep}, batch {k}: ids differ"
+            assert o.plen.tolist() == single[k][1], (rep, k)
+        assert runner.gave_up == 0
+        assert sorted(b for _, b in runner.assign) == list(range(len(batches)))
+        assert sorted(i for i, _ in runner.assign) == [0, 0, 0, 1, 1, 1], runner.assign
+
+
 def test_prompts_beside_grids_deterministic(cuda):
     """The sound-effect prompt (prompt_kernel, gpt2.hip) computed on ten streams while ten
     persistent decode grids run on ten others equals the prompt computed alone, for all 1045

@@ -3,16 +3,15 @@
 decode) repeated for several arms, interleaved, so box-to-box and run-to-run spread cancel.
 
 An arm is "name:inflight:knob=v,knob=v[:grids[:budget[:encode_ahead]]]" (zs_tune_set knobs, reset
-(runner options among the knobs: late=0 sizes each grid at its batch's begin instead of at its
-launch; spread=1: exclusive one-CU-per-workgroup grids while the CUs allow; prio=0: default stream
-priorities instead of high for the pipelines and low for the encoder; extra=k: k pipelines beyond
-the grids the budget holds; one=0: begin every idle pipeline in one pass instead of one per pass; eg=0: encoder passes
-enqueued kernel by kernel instead of replayed from a hipGraph)
+(runner options among the knobs: prio=0: default stream priorities instead of high for the
+pipelines and low for the encoder; extra=k: k pipelines beyond the grids the budget holds)
 to the baseline values given with --base between arms; grids: the persistent-decode grid sizes the
 runner may use, zsaac.pipeline.persist_grids, e.g. "48" or "96-48" ('-'-separated); budget:
 workgroup slots of the in-flight grids; encode_ahead: clips per up-front encoder pass, 0 = each
-batch encodes its own clips, suffix "f": every begin waits for the whole encode; a 7th field "bf":
-begin_first, every pipeline begins at once and the launches follow within the budget); every arm runs on one shared set of streams.
+batch encodes its own clips; a 7th field "bf": begin_first, every pipeline begins at once and the
+launches follow within the budget); every arm runs on one shared set of streams.  The runner
+options late / spread / one / eg and the encode_ahead suffix "f" are gone with the switches they
+set (their measurements: profiles/r5/headline_ab_*.txt, profiles/r6/begin_first_ab.txt).
 
     python tools/headline_ab.py --reps 6 "b512:10::48:512" "base:5::48:256" "l64:5:lean_min128=64"
 """
@@ -37,10 +36,16 @@ from zsaac.pipeline import ConcurrentRunner, persist_grids  # noqa: E402
 os.environ["GPU_MAX_HW_QUEUES"] = os.environ.get("AB_HW_QUEUES", "16")
 
 
+REMOVED = ("late", "spread", "one", "eg")    # runner switches that no longer exist
+
+
 def knobs(spec):
     out = {}
     for kv in filter(None, spec.split(",")):
         k, v = kv.split("=")
+        if k.strip() in REMOVED:
+            sys.exit(f"headline_ab: the runner option {k.strip()!r} was removed with its switch "
+                     "(ConcurrentRunner keeps the measured winner); drop it from the arm")
         out[k.strip()] = int(v)
     return out
 
@@ -71,20 +76,18 @@ def main():
     for spec in a.arms:
         name, inflight, kn, *sh = spec.split(":")
         kn = knobs(kn)
+        if len(sh) > 2 and sh[2].endswith("f"):
+            sys.exit(f"headline_ab: encode_ahead {sh[2]!r}: the 'f' suffix (every begin waits for "
+                     "the whole encode) was removed from ConcurrentRunner")
         streams, enc_stream = sets[kn.pop("prio", 1)]
         r = ConcurrentRunner(pipe, int(inflight), streams=streams, enc_stream=enc_stream,
                              extra_pipes=kn.pop("extra", 0),
                              grids=persist_grids(sh[0].replace("-", ",")) if sh and sh[0] else None,
                              budget=int(sh[1]) if len(sh) > 1 and sh[1] else None,
-                             encode_ahead=int(sh[2].rstrip("f")) if len(sh) > 2 and sh[2] else 0,
-                             encode_first=len(sh) > 2 and sh[2].endswith("f"),
+                             encode_ahead=int(sh[2]) if len(sh) > 2 and sh[2] else 0,
                              begin_first=len(sh) > 3 and sh[3] == "bf")
         for size in sorted({b.shape[0] for b in batches}, reverse=True):
             r.warmup(next(b for b in batches if b.shape[0] == size))
-        r.late_grid = bool(kn.pop("late", 1))      # runner options, not zs_tune_set knobs
-        r.spread = bool(kn.pop("spread", 0))
-        r.one_begin = bool(kn.pop("one", 1))
-        r.enc_graph = bool(kn.pop("eg", 1))
         arms.append((name, r, kn))
     res = {n: [] for n, _, _ in arms}
     for rep in range(a.reps + 1):

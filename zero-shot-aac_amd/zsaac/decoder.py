@@ -677,7 +677,7 @@ class Gpt2Decoder:
 
     def greedy_begin_device(self, R: int):
         """The device work of :meth:`greedy_begin` (LM head, step-0 bookkeeping): no host
-        state, so a pipeline can capture it in its begin graph."""
+        state."""
         ops.lmhead_topk(self.hf[:R], self.w.wte, 1, None, self.pval1, self.pidx1,
                         temperature=self.temperature)
         ops.greedy_init(R, self.plen, self.pos, self.done, self.out_len, self.out_ids,

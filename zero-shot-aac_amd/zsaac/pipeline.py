@@ -16,7 +16,7 @@ import dataclasses
 import os
 import time
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -218,8 +218,6 @@ class CaptionPipeline:
         self.embed = torch.empty(B * self.Pmax, 768, device=dev)
         self.prefix_ids = torch.zeros(B * self.Pmax, **i32)
         self.emb_buf = torch.empty(B, 1024, device=dev)
-        self.emb_in = torch.empty(B, 1024, device=dev)     # begin_emb_graphed's input
-        self._begin_graphs = {}
 
     def _setup_tables(self, label_table, label_tokens):
         cfg, dev = self.cfg, self.dev
@@ -286,45 +284,9 @@ class CaptionPipeline:
     def begin_emb(self, emb: torch.Tensor):
         """Enqueue prompt assembly, mapper, prefill, get_prefix_tokens and decode step 0 for a
         batch of CLAP embeddings, without any host synchronisation."""
-        cfg, B = self.cfg, emb.shape[0]
+        cfg, B, Pmax = self.cfg, emb.shape[0], self.Pmax
         self._B, self._emb = B, emb
         assert B <= cfg.batch
-        self._begin_device(emb)
-        dec = self.decoder
-        if cfg.beam:
-            dec.beam_begin(B, cfg.beam)
-        else:
-            dec.greedy_begin_host(B)
-
-    def begin_emb_graphed(self, emb: torch.Tensor):
-        """begin_emb with its device work (prompt .. step 0: ~100 kernels) replayed from a hipGraph
-        per batch size, captured on first use on the current (non-default) stream: the embedding
-        is copied into a fixed buffer first, every other operand already lives in this pipeline's
-        buffers.  Greedy decoding only (beam search: begin_emb).  A kernel trace of the headline
-        showed a begin's stream idle between its kernels for 50-75 % of the begin's wall time
-        (tools/tl_phases.py: 14-30 ms wall, 5-13 ms of kernels beside the decode grids)."""
-        cfg, B = self.cfg, emb.shape[0]
-        assert B <= cfg.batch and not cfg.beam
-        self.emb_in[:B].copy_(emb)
-        if not hasattr(self, "_begin_graphs"):
-            self._begin_graphs = {}
-        g = self._begin_graphs.get(B)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            g.capture_begin()
-            try:
-                self._begin_device(self.emb_in[:B])
-            finally:
-                g.capture_end()
-            self._begin_graphs[B] = g
-            self.decoder.n_captures += 1
-        g.replay()
-        self._B, self._emb = B, self.emb_in[:B]
-        self.decoder.greedy_begin_host(B)
-
-    def _begin_device(self, emb: torch.Tensor):
-        """The device work of a begin (no host state: capturable)."""
-        cfg, B, Pmax = self.cfg, emb.shape[0], self.Pmax
         ops.prompt_assemble(emb, self.labels, cfg.sound_effect_num, self.label_tok, self.label_len,
                             self.hard_ids[:B], self.hard_len[:B])
         prefix = self.prefix[:B]
@@ -341,9 +303,10 @@ class CaptionPipeline:
             self.prefix_tokens(B, soft)
         if cfg.beam:
             dec.prefill(B, Pmax, row_stride=cfg.beam)
+            dec.beam_begin(B, cfg.beam)
         else:
             dec.prefill(B, Pmax)
-            dec.greedy_begin_device(B)
+            dec.greedy_begin(B)
 
 
 def persist_grids(env: Optional[str] = None) -> List[int]:
@@ -406,26 +369,88 @@ STALL_S = float(os.environ.get("ZSAAC_RUNNER_STALL_S", "60"))
 STAGGER_US = int(os.environ.get("ZSAAC_STAGGER_US", "200"))
 
 
+class SlotAccount:
+    """What a run's persistent grids hold of the chip (host bookkeeping only): the workgroup
+    slots of the grids in flight against ``budget``, which of the ``pool`` streams has a grid
+    running on it, and -- the small-run path -- the workgroups launched exclusive (one CU each)
+    against ``excl_cap`` CUs."""
+
+    def __init__(self, grids: List[int], budget: int, pool: int, excl_cap: int = 0):
+        self.grids, self.budget, self.pool, self.excl_cap = list(grids), budget, pool, excl_cap
+        self.used = self.excl = 0
+        self.busy = set()
+
+    def admit(self, unlaunched: int) -> Optional[Tuple[int, int]]:
+        """Takes room for the next batch's grid, ``unlaunched`` batches (it included) still to
+        launch: (its size by choose_persist_grid, the index of a stream no grid is running on),
+        or None while every stream is busy or that grid does not fit the budget."""
+        if len(self.busy) >= self.pool:
+            return None
+        g = choose_persist_grid(self.used, unlaunched, self.grids, self.budget)
+        if self.used + g > self.budget:
+            return None
+        k = next(k for k in range(self.pool) if k not in self.busy)
+        self.used += g
+        self.busy.add(k)
+        return g, k
+
+    def exclusive(self, g: int) -> bool:
+        """Whether the grid just admitted takes one CU per workgroup (counted if so): while the
+        exclusive workgroups in flight leave it the CUs (it shares CUs with normal grids only)."""
+        if self.excl + g > self.excl_cap:
+            return False
+        self.excl += g
+        return True
+
+    def release(self, grid: int = 0, excl: int = 0, stream: Optional[int] = None):
+        self.used -= grid
+        self.excl -= excl
+        self.busy.discard(stream)
+
+
+@dataclass(eq=False)
+class _InFlight:
+    """A batch between its begin and its result copy (compared by identity)."""
+    dec: Gpt2Decoder                  # decodes it: a pipeline's decoder or a group twin's sub-decoder
+    result: Callable[[], CaptionBatch]    # views of its outputs
+    batch: int
+    owner: int                        # its pipeline's / group's index, as ``assign`` reports it
+    stream: Optional[torch.cuda.Stream] = None    # its decode chunks and result copy run here
+    begun: Optional[torch.cuda.Event] = None      # its begin's end (persistent launch deferred)
+    k: Optional[int] = None           # the stream index the slot account gave its launch
+    grid: int = 0                     # workgroups its launch holds (0: none, or it gave up)
+    excl: int = 0                     # of those, exclusive ones
+    join: Optional[torch.cuda.Stream] = None      # the launch's stream while ``stream`` has not joined it
+    chunks: int = 0                   # decode chunks enqueued after the launch
+    ev: Optional[torch.cuda.Event] = None         # finished_async's of the last enqueue: the event
+    flag: Optional[torch.Tensor] = None           # and the pinned flags valid after it
+    done: bool = False
+
+
 class ConcurrentRunner:
     """Keeps several independent bs=`cfg.batch` batches in flight on one GPU; the host only
-    polls events and a pinned all-done flag (no blocking syncs).  Two schedules:
+    polls events and a pinned all-done flag (no blocking syncs).  Three schedules, each a short
+    driver (when begins are enqueued, which stream a grid takes, gating) around one launch
+    (_launch), one poll (_poll), one slot account (SlotAccount) and one idle / watchdog / trace
+    helper (_idle, _note):
 
-    * pipelined (run's main loop): pipeline twins (shared weights, private buffers / KV cache /
-      graphs), each on its own HIP stream; a batch's begin (encode .. step 0) is enqueued when a
-      pipeline frees, its persistent decode grid when the begin has finished -- begins and grids
-      share the chip.  Also the path of a run with no more batches than grids fit at once.
-    * staged (begin_first, the bench's headline schedule; _run_grouped with begin_group, else
-      _run_staged): every begin runs first -- with begin_group k, one begin per k consecutive
-      batches on a group twin, each batch decoding on a sub-decoder that shares the twin's KV
-      cache rows -- and the decode grids launch once every begin has finished, in batch order as
-      the budget frees, on a pool of budget / 48 streams, the first wave released STAGGER_US
-      apart.  Ids are the same under either schedule (tests/test_gpu_persist.py).
+    * pipelined (run): pipeline twins (shared weights, private buffers / KV cache / graphs),
+      each on its own HIP stream; a batch's begin (encode .. step 0) is enqueued when a pipeline
+      frees, its persistent decode grid when the begin has finished -- begins and grids share
+      the chip.  Also the path of a run with no more batches than grids fit at once.
+    * staged (begin_first; _run_staged): a begin on every free pipeline first, the decode grids
+      launched in batch order as the budget frees, on a pool of budget / 48 streams, the first
+      wave after the gating begins and released STAGGER_US apart.
+    * grouped (begin_first with begin_group k, the bench's headline schedule; _run_grouped):
+      staged with one begin per k consecutive batches on a group twin, each batch decoding on a
+      sub-decoder that shares the twin's KV cache rows.
 
-    Results are copied out on the pipeline's stream before it takes the next batch."""
+    Ids are the same under every schedule (tests/test_gpu_persist.py).  Results are copied out
+    on the batch's stream before its pipeline takes the next batch."""
 
     def __init__(self, pipe: CaptionPipeline, n_inflight: int = 2, streams: Optional[list] = None,
                  grids: Optional[List[int]] = None, budget: Optional[int] = None,
-                 encode_ahead: int = 0, encode_first: bool = False, begin_first: bool = False,
+                 encode_ahead: int = 0, begin_first: bool = False,
                  extra_pipes: int = 0, enc_stream=None, cu_split: int = 0,
                  begin_gate: int = 0, begin_group: int = 0, n_batches: int = 0):
         self.cus = torch.cuda.get_device_properties(pipe.dev).multi_processor_count
@@ -451,19 +476,6 @@ class ConcurrentRunner:
                             and isinstance(pipe.mapper, MlpMapper) else 0)
         self.n_batches = int(n_batches)
         self.gpipes: List[CaptionPipeline] = []
-        self.late_grid = True     # grid size chosen when the begin has finished (False: at begin)
-        # one begin per pass over the pipelines: a begin costs milliseconds of host enqueue, so
-        # beginning every idle pipeline in one pass delayed the first grids' launches until the
-        # last begin was enqueued (~43 ms into the headline, tools/timeline.py)
-        self.one_begin = True
-        # the encoder's up-front passes replayed from per-size hipGraphs (Encoder.encode_graphed)
-        self.enc_graph = True
-        self.spread = False       # A/B: exclusive (one CU per workgroup) grids while CUs allow
-        # A/B (ZSAAC_GRAPH_BEGINS=1): greedy begins replayed from per-pipeline hipGraphs
-        # (CaptionPipeline.begin_emb_graphed), captured in warmup -- measured 5.75k vs 5.86k and
-        # 5.09k vs 5.30k clips/s (same box, medians of 5): the idle time between a begin's kernels
-        # beside the grids is waiting for CU resources, not host enqueue
-        self.graph_begins = self.persist and os.environ.get("ZSAAC_GRAPH_BEGINS", "0") != "0"
         if self.persist and (not self.begin_first or self.begin_group):
             # persistent decode grids must be co-resident: at most budget // (smallest grid)
             n_inflight = max(1, min(n_inflight, self.budget // self.grids[-1]))
@@ -477,10 +489,7 @@ class ConcurrentRunner:
         # batches), on a stream of its own; a batch's begin (mapper .. step 0) waits only for its
         # own pass.  The encoder then runs at its most efficient size and before the decode grids
         # fill the chip; captions do not depend on it (a clip's embedding is its own).
-        # encode_first: every begin waits for the LAST pass (encoding and decoding do not share
-        # the chip).
         self.encode_ahead = int(encode_ahead) if pipe.encoder is not None else 0
-        self.encode_first = bool(encode_first)
         self.enc = pipe.encoder.twin(max_batch=self.encode_ahead) if self.encode_ahead else None
         # dedicated streams on distinct hardware queues: pooled torch streams take their queue at
         # first use and can end up sharing one, which serializes the batches
@@ -520,35 +529,22 @@ class ConcurrentRunner:
                                else ops.dedicated_streams(1, pipe.dev, priority=1)[0])
 
     def warmup(self, wav: torch.Tensor):
-        """Runs one batch per pipeline synchronously (captures every decode graph, and with
-        graph_begins the begin graph of this batch size)."""
-        for i, p in enumerate(self.pipes):
-            s = self.streams[i % len(self.streams)]
-            s.wait_stream(torch.cuda.current_stream(p.dev))
-            with torch.cuda.stream(s):
-                if self.graph_begins:
-                    p.begin_emb(p.encode(wav))          # (eager first: every lazy buffer exists)
-                    p.decoder.run_to_completion()
-                    p.begin_emb_graphed(p.encode(wav))
-                    p.decoder.run_to_completion()
-                else:
-                    p.caption_wav(wav)
-                p.decoder.capture_buckets()
-            s.synchronize()
-        self._warm_groups(wav, "wav")
+        """Runs one batch per pipeline (and per group twin) synchronously: captures every decode
+        graph."""
+        self._warm(wav, "wav")
 
     def warmup_emb(self, emb: torch.Tensor):
+        self._warm(emb, "emb")
+
+    def _warm(self, x: torch.Tensor, inputs: str):
         for i, p in enumerate(self.pipes):
             s = self.streams[i % len(self.streams)]
             s.wait_stream(torch.cuda.current_stream(p.dev))
             with torch.cuda.stream(s):
-                p.caption_emb(emb)
-                if self.graph_begins:
-                    p.begin_emb_graphed(emb)
-                    p.decoder.run_to_completion()
+                (p.caption_wav if inputs == "wav" else p.caption_emb)(x)
                 p.decoder.capture_buckets()
             s.synchronize()
-        self._warm_groups(emb, "emb")
+        self._warm_groups(x, inputs)
 
     def decoders(self) -> List[Gpt2Decoder]:
         """Every decoder this runner steps: the pipelines' and the group twins' sub-decoders."""
@@ -577,6 +573,139 @@ class ConcurrentRunner:
                     d.run_to_completion()
             s.synchronize()
 
+    # ------------------------------------------------------------------ shared by the schedules
+    def _start(self, n: int, keep, caller, slots: SlotAccount, schedule: str):
+        """A run's bookkeeping, reset."""
+        self.decode_steps = [0] * n      # per batch: decode steps actually enqueued
+        self.assign = []                 # (pipeline / group index, batch index), in begin / launch order
+        self.grid = [0] * n              # persistent grid size per batch (0: none)
+        self.gave_up = 0                 # launches of this run that resumed stepwise
+        self.trace = [] if os.environ.get("ZSAAC_RUNNER_TRACE") else None   # (kind, index, ms)
+        self._results: List[Optional[CaptionBatch]] = [None] * n
+        self._keep, self._caller, self._slots, self._schedule = keep, caller, slots, schedule
+        self._t_run = self._t_prog = time.perf_counter()
+
+    def _finish(self, streams, ahead=None) -> List[CaptionBatch]:
+        """The end of a run: the caller's stream, which consumes the results, joins ``streams``."""
+        for s in streams:
+            self._caller.wait_stream(s)
+        if ahead is not None:
+            self._caller.wait_stream(self.enc_stream)
+        results, self._results, self._keep = self._results, None, None
+        return results
+
+    def _note(self, kind: str, index: int):
+        if self.trace is not None:
+            self.trace.append((kind, index, round((time.perf_counter() - self._t_run) * 1e3, 2)))
+
+    def _idle(self, progressed: bool, waiting, active):
+        """The end of a driver's pass: after one that moved nothing, a short sleep, and a
+        RuntimeError (with the run's state) once nothing has moved for STALL_S."""
+        if progressed:
+            self._t_prog = time.perf_counter()
+            return
+        time.sleep(20e-6)
+        if time.perf_counter() - self._t_prog > STALL_S:
+            sl = self._slots
+            raise RuntimeError(
+                f"ConcurrentRunner ({self._schedule}): no progress for {STALL_S} s; waiting "
+                f"(batch, owner) {[(r.batch, r.owner) for r in waiting][:8]}, in flight (batch, "
+                f"owner, chunks, stream, grid; no stream: begun, not launched) "
+                f"{[(r.batch, r.owner, r.chunks, r.k, r.grid) for r in active]}, "
+                f"{sl.used} of {sl.budget} slots, streams busy {sorted(sl.busy)} of {sl.pool}")
+
+    def _begin(self, i, bi, batches, inputs, ahead, after=None):
+        """Batch bi's begin on pipeline i's stream (``after``: an event it waits for first),
+        enqueued kernel by kernel: replayed from a hipGraph per pipeline the headline measured
+        5.75k vs 5.86k and 5.09k vs 5.30k clips/s (same box, medians of 5) -- the idle time
+        between a begin's kernels beside the grids is waiting for CU resources, not host enqueue."""
+        p, s = self.pipes[i], self.streams[i % len(self.streams)]
+        with torch.cuda.stream(s):
+            if after is not None:
+                s.wait_event(after)
+            if ahead is not None:
+                s.wait_event(ahead.ready(bi))
+                p.begin_emb(ahead.embs[bi])
+            elif inputs == "wav":
+                p.begin_emb(p.encode(batches[bi]))
+            else:
+                p.begin_emb(batches[bi])
+
+    def _launch(self, r: _InFlight, g: int, s, waits=(), rank: Optional[int] = None,
+                exclusive: bool = False):
+        """Enqueues r's persistent launch, a grid of g workgroups, on stream s after the events
+        ``waits``, held back rank x STAGGER_US (rank None: a launch outside the first wave)."""
+        d = r.dec
+        d.persist_grid, d.persist_exclusive = g, exclusive     # (never a value left over)
+        r.grid, r.excl = g, g if exclusive else 0
+        self.grid[r.batch] = g
+        with torch.cuda.stream(s):
+            for ev in waits:
+                s.wait_event(ev)
+            if rank is not None and STAGGER_US:
+                ops.stream_spin(STAGGER_US * rank, s)
+            d.launch_pending()
+            r.ev, r.flag = d.finished_async()
+        r.join = s if s is not r.stream else None
+        self._note("launch", r.batch)
+
+    def _launch_waiting(self, waiting: List[_InFlight], later: int, gate) -> List[_InFlight]:
+        """The staged schedules' launches: the waiting batches in order while the slot account
+        admits them (``later``: batches not begun yet), each on a stream no grid is running on,
+        after its own begin and -- the first wave -- the gating begins' events, released in turn."""
+        out = []
+        while waiting:
+            got = self._slots.admit(len(waiting) + later)
+            if got is None:
+                break
+            r = waiting.pop(0)
+            g, r.k = got
+            r.stream = self.streams[r.k]
+            self._launch(r, g, r.stream, [r.begun, *gate],
+                         len(self._slots.busy) - 1 if gate else None)
+            out.append(r)
+        return out
+
+    def _poll(self, r: _InFlight) -> bool:
+        """Moves a launched batch on if its last enqueue has finished (else False): a launch that
+        gave up resumes on the phase launches, a finished batch is copied out (r.done), any other
+        takes its next chunk."""
+        if not r.ev.query():
+            return False
+        d, s, flag = r.dec, r.stream, r.flag
+        if r.join is not None:
+            s.wait_stream(r.join)            # (cu_split: the grid ran on a stream of its own)
+            r.join = None
+        if int(flag[1]) < 0:
+            # the persistent launch gave up waiting (its grid was not co-resident): finish this
+            # batch on the per-step path from the state it started from
+            self.gave_up += 1
+            with torch.cuda.stream(s):
+                d.resume_stepwise()
+                d.step_chunk(None)
+                r.ev, r.flag = d.finished_async()
+            self._slots.release(r.grid, r.excl)
+            r.grid = r.excl = 0
+            r.chunks = 1
+        elif int(flag[0]) or r.chunks >= d.n_chunks:
+            d.note_persist_steps(int(flag[3]))
+            self.decode_steps[r.batch] = (int(flag[3]) if not self.pipes[0].cfg.beam
+                                          else 1 + r.chunks * d.chunk)
+            self._note("done", r.batch)
+            with torch.cuda.stream(s):
+                out = self._results[r.batch] = _copy_batch(r.result(), self._caller)
+                if self._keep is not None:
+                    self._keep(out)
+            self._slots.release(r.grid, r.excl, r.k)
+            r.done = True
+        else:
+            with torch.cuda.stream(s):
+                d.step_chunk(int(flag[2]))
+                r.ev, r.flag = d.finished_async()
+            r.chunks += 1
+        return True
+
+    # ------------------------------------------------------------------ the schedules
     def run(self, batches: Sequence[torch.Tensor], keep=None, inputs: str = "wav") -> List[CaptionBatch]:
         """Captions every batch (waveforms [B, n] or, with inputs="emb", CLAP embeddings
         [B, 1024]; B <= cfg.batch, ragged last batch allowed); returns CaptionBatch copies in
@@ -585,18 +714,18 @@ class ConcurrentRunner:
         run() instead, in input order — see bench.py)."""
         assert inputs in ("wav", "emb")
         self.bdec = None                 # (_run_grouped: batch -> the sub-decoder that decoded it)
-        results: List[Optional[CaptionBatch]] = [None] * len(batches)
+        n = len(batches)
         caller = torch.cuda.current_stream(self.pipes[0].dev)
         for s in self.streams:           # inputs were produced on the caller's stream
             s.wait_stream(caller)
-        staged = self.begin_first and len(batches) > self.budget // self.grids[-1]
+        staged = self.begin_first and n > self.budget // self.grids[-1]
         ahead = None
-        if inputs == "wav" and self.enc is not None and not staged and len(batches) > len(self.pipes):
+        if inputs == "wav" and self.enc is not None and not staged and n > len(self.pipes):
             # (a pipelined run that fits its pipelines at once begins sooner encoding per batch:
             # measured on a 131-clip shard, 37.5 vs 40 ms.  A staged run encodes on its begins'
             # streams: with the encoder's passes on their low-priority stream every repetition
             # took 2-32 s instead of 0.15 s -- profiles/r6/begin_first_ab.txt, r6i)
-            ahead = self._encode_ahead(batches, caller)
+            ahead = _EncodeAhead(self, batches, caller)
         if staged and self.begin_group:
             return self._run_grouped(batches, keep, inputs, caller)
         if staged:
@@ -607,143 +736,67 @@ class ConcurrentRunner:
         # for: its grids may fill the chip, and they take one CU per workgroup (exclusive
         # launches) while the CUs allow -- left to itself the dispatcher doubles workgroups up on
         # CUs while others idle (tools/placement.py: 3 grids of 96 covered 185 CUs, 103 twice)
-        small = self.persist and len(batches) <= len(self.pipes)
-        exclusive = False
-        spread = self.spread or small
-        budget = 2 * self.cus if small else self.budget
-        excl_slots = {}
-        excl_in_flight = lambda: sum(excl_slots.values())
-        active = {}
+        small = self.persist and n <= len(self.pipes)
+        # (a pipeline decodes on its own stream: the account's stream index only counts it)
+        slots = SlotAccount(self.grids, 2 * self.cus if small else self.budget, len(self.pipes),
+                            excl_cap=self.cus if small else 0)
+        self._start(n, keep, caller, slots, "pipelined")
+        active = {}                      # pipeline index -> its batch
         nxt = 0
-        trace = self.trace = [] if os.environ.get("ZSAAC_RUNNER_TRACE") else None
-        t_run = time.perf_counter()
-        self.decode_steps = [0] * len(batches)     # per batch: decode steps actually enqueued
-        self.assign = []                           # (pipeline index, batch index), in begin order
-        self.grid = [0] * len(batches)             # persistent grid size per batch (0: none)
-        self.gave_up = 0                           # launches of this run that resumed stepwise
-        slots = {}                                 # pipeline index -> its launch's workgroups
-        while nxt < len(batches) or active:
+        while nxt < n or active:
             progressed = False
             if ahead is not None:
                 ahead.pump()
             for i, (p, s) in enumerate(zip(self.pipes, self.streams)):
-                st = active.get(i)
-                if st is None:
-                    if nxt < len(batches):
-                        # persistent decode: the begin is enqueued now, the grid launch when the
-                        # begin has finished (its size chosen then, from the grids in flight and
-                        # the batches not yet launched: bigger grids once few batches remain)
-                        if self.persist and not self.late_grid:    # (A/B: size at begin)
-                            g = choose_persist_grid(sum(slots.values()), len(batches) - nxt,
-                                                    self.grids, budget)
-                            self.grid[nxt] = slots[i] = g
-                            p.decoder.persist_grid = g
-                            p.decoder.persist_exclusive = exclusive
-                        p.decoder.defer_launch = self.persist and self.late_grid
-                        try:
-                            self._begin(i, nxt, batches, inputs, ahead)
-                        finally:
-                            p.decoder.defer_launch = False
-                        with torch.cuda.stream(s):
-                            if self.persist and self.late_grid:
-                                ev = torch.cuda.Event()
-                                ev.record(s)
-                                active[i] = ("begun", nxt, ev)
-                            else:
-                                ev, flag = p.decoder.finished_async()
-                                active[i] = (nxt, 0, ev, flag)
-                        self.assign.append((i, nxt))
-                        if trace is not None:
-                            trace.append(("begin", nxt, round((time.perf_counter() - t_run) * 1e3, 2)))
-                        nxt += 1
-                        progressed = True
-                        if self.one_begin:
-                            break       # launches / completions before the next begin
-                    continue
-                if st[0] == "begun":
-                    _, bi, ev = st
-                    if not ev.query():
+                r = active.get(i)
+                if r is None:
+                    if nxt == n:
                         continue
-                    unlaunched = len(batches) - nxt + sum(1 for a in active.values()
-                                                          if a[0] == "begun")
-                    g = choose_persist_grid(sum(slots.values()), unlaunched, self.grids,
-                                            budget)
-                    if sum(slots.values()) + g > budget:
-                        continue               # (extra pipelines: wait for a grid to finish)
-                    # spread (A/B option): while the exclusive workgroups in flight leave room,
-                    # a grid takes one CU per workgroup (it shares CUs with normal grids only)
-                    excl = exclusive or (spread and excl_in_flight() + g <= self.cus)
-                    p.decoder.persist_grid = g
-                    p.decoder.persist_exclusive = excl
-                    slots[i] = g
-                    excl_slots[i] = g if excl else 0
-                    self.grid[bi] = g
+                    # persistent decode: the begin is enqueued now, the grid launch when the
+                    # begin has finished (its size chosen then, from the grids in flight and
+                    # the batches not yet launched: bigger grids once few batches remain; sized
+                    # at the begin the headline ran 5.61k against 5.73k clips/s, budget 384,
+                    # medians of 12: profiles/r5/headline_ab_budget_late.txt)
+                    r = active[i] = _InFlight(p.decoder, p.result, nxt, i, s)
+                    p.decoder.defer_launch = self.persist
+                    try:
+                        self._begin(i, nxt, batches, inputs, ahead)
+                    finally:
+                        p.decoder.defer_launch = False
+                    if self.persist:
+                        r.begun = torch.cuda.Event()
+                        r.begun.record(s)
+                    else:
+                        with torch.cuda.stream(s):
+                            r.ev, r.flag = p.decoder.finished_async()
+                    self.assign.append((i, nxt))
+                    self._note("begin", nxt)
+                    nxt += 1
+                    progressed = True
+                    # one begin per pass over the pipelines, launches and completions before the
+                    # next: a begin costs milliseconds of host enqueue, so beginning every idle
+                    # pipeline in one pass delayed the first grids' launches until the last begin
+                    # was enqueued (~43 ms into the headline, tools/timeline.py; the A/B
+                    # among profiles/r5/headline_ab_*.txt)
+                    break
+                if r.ev is None:         # begun, its grid not launched yet
+                    if not r.begun.query():
+                        continue
+                    got = slots.admit(n - nxt + sum(1 for a in active.values() if a.ev is None))
+                    if got is None:
+                        continue         # (extra pipelines: wait for a grid to finish)
+                    g, r.k = got
                     gs = self.gstreams[i] if self.gstreams else s
                     if gs is not s:
                         gs.wait_stream(s)
-                    with torch.cuda.stream(gs):
-                        p.decoder.launch_pending()
-                        ev, flag = p.decoder.finished_async()
-                    active[i] = (bi, 0, ev, flag)
-                    if trace is not None:
-                        trace.append(("launch", bi, round((time.perf_counter() - t_run) * 1e3, 2)))
+                    self._launch(r, g, gs, exclusive=small and slots.exclusive(g))
                     progressed = True
-                    continue
-                bi, n, ev, flag = st
-                if not ev.query():
-                    continue
-                progressed = True
-                if self.gstreams and n == 0:
-                    s.wait_stream(self.gstreams[i])   # (the grid ran on its own stream)
-                if int(flag[1]) < 0:
-                    # the persistent launch gave up waiting (its grid was not co-resident): finish
-                    # this batch on the per-step path from the state it started from
-                    self.gave_up += 1
-                    with torch.cuda.stream(s):
-                        p.decoder.resume_stepwise()
-                        p.decoder.step_chunk(None)
-                        ev, flag = p.decoder.finished_async()
-                    slots.pop(i, None)
-                    excl_slots.pop(i, None)
-                    active[i] = (bi, 1, ev, flag)
-                    continue
-                if int(flag[0]) or n >= p.decoder.n_chunks:
-                    p.decoder.note_persist_steps(int(flag[3]))
-                    self.decode_steps[bi] = int(flag[3]) if not p.cfg.beam else 1 + n * p.decoder.chunk
-                    with torch.cuda.stream(s):
-                        r = p.result()
-                        results[bi] = _copy_batch(r, caller)
-                        if keep is not None:
-                            keep(results[bi])
-                    del active[i]
-                    slots.pop(i, None)
-                    excl_slots.pop(i, None)
-                else:
-                    with torch.cuda.stream(s):
-                        p.decoder.step_chunk(int(flag[2]))
-                        ev, flag = p.decoder.finished_async()
-                    active[i] = (bi, n + 1, ev, flag)
-            if not progressed:
-                time.sleep(20e-6)
-        for s in self.streams:           # results are consumed on the caller's stream
-            caller.wait_stream(s)
-        for s in self.gstreams or []:
-            caller.wait_stream(s)
-        if ahead is not None:
-            caller.wait_stream(self.enc_stream)
-        return results
-
-    def _begin(self, i, bi, batches, inputs, ahead):
-        p, s = self.pipes[i], self.streams[i % len(self.streams)]
-        begin = p.begin_emb_graphed if self.graph_begins else p.begin_emb
-        with torch.cuda.stream(s):
-            if ahead is not None:
-                s.wait_event(ahead.ready(bi))
-                begin(ahead.embs[bi])
-            elif inputs == "wav":
-                begin(p.encode(batches[bi]))
-            else:
-                begin(batches[bi])
+                elif self._poll(r):
+                    progressed = True
+                    if r.done:
+                        del active[i]
+            self._idle(progressed, (), active.values())
+        return self._finish(self.streams + (self.gstreams or []), ahead)
 
     def _run_staged(self, batches, keep, inputs, caller, ahead):
         """run() with begin_first: a begin on every free pipeline (persistent launches deferred),
@@ -752,115 +805,54 @@ class ConcurrentRunner:
         stream no grid is running on, after its own begin and -- the first ones -- after the
         first `begin_gate` begins (0: every begin of the first round) have finished on the GPU.
         With a pipeline per batch every begin runs before (or beside few) decode grids and every
-        later launch finds its batch begun."""
-        n = len(batches)
-        S = len(self.streams)
-        results: List[Optional[CaptionBatch]] = [None] * n
-        self.decode_steps = [0] * n
-        self.assign, self.grid, self.gave_up = [], [0] * n, 0
+        later launch finds its batch begun.  With fewer, a pipeline's next begin waits for its
+        last batch's result copy (which ran on the grid's stream, not the pipeline's)."""
+        n, S = len(batches), len(self.streams)
+        self._start(n, keep, caller, SlotAccount(self.grids, self.budget, S), "begin_first")
         free = list(range(len(self.pipes)))
         n_gate = min(n, len(free)) if self.begin_gate <= 0 else min(n, self.begin_gate)
-        begun, active, slots = [], {}, {}
-        gate, bev, sbusy = [], {}, set()
+        waiting, active, gate = [], [], []
+        copied = {}                      # pipeline index -> the event after its last result copy
         nxt = 0
-        trace = self.trace = [] if os.environ.get("ZSAAC_RUNNER_TRACE") else None
-        t_run = t_prog = time.perf_counter()
-        while nxt < n or begun or active:
+        while nxt < n or waiting or active:
             progressed = False
             if ahead is not None:
                 ahead.pump()
             if nxt < n and free:
                 i = free.pop(0)
-                self.pipes[i].decoder.defer_launch = True
+                p = self.pipes[i]
+                p.decoder.defer_launch = True
                 try:
-                    self._begin(i, nxt, batches, inputs, ahead)
+                    self._begin(i, nxt, batches, inputs, ahead, after=copied.pop(i, None))
                 finally:
-                    self.pipes[i].decoder.defer_launch = False
-                ev = torch.cuda.Event()
-                ev.record(self.streams[i % S])
-                bev[nxt] = ev
+                    p.decoder.defer_launch = False
+                r = _InFlight(p.decoder, p.result, nxt, i, begun=torch.cuda.Event())
+                r.begun.record(self.streams[i % S])
                 if len(gate) < n_gate:
-                    gate.append(ev)
-                begun.append((nxt, i))
+                    gate.append(r.begun)
+                waiting.append(r)
                 self.assign.append((i, nxt))
-                if trace is not None:
-                    trace.append(("begin", nxt, round((time.perf_counter() - t_run) * 1e3, 2)))
+                self._note("begin", nxt)
                 nxt += 1
                 progressed = True
-            while begun and len(gate) >= n_gate and len(sbusy) < S:
-                bi, i = begun[0]
-                used = sum(slots.values())
-                g = choose_persist_grid(used, len(begun) + n - nxt, self.grids, self.budget)
-                if used + g > self.budget:
-                    break
-                k = next(k for k in range(S) if k not in sbusy)
-                p, s = self.pipes[i], self.streams[k]
-                p.decoder.persist_grid = g
-                p.decoder.persist_exclusive = False    # (not a value left over from run())
-                with torch.cuda.stream(s):
-                    s.wait_event(bev.pop(bi))
-                    for ev in gate:          # the first launches: after the gating begins
-                        s.wait_event(ev)
-                    if gate and STAGGER_US:      # (released in turn, as _run_grouped)
-                        ops.stream_spin(STAGGER_US * len(sbusy), s)
-                    p.decoder.launch_pending()
-                    ev, flag = p.decoder.finished_async()
-                slots[i] = g
-                sbusy.add(k)
-                self.grid[bi] = g
-                active[i] = (bi, 0, ev, flag, k)
-                begun.pop(0)
-                if trace is not None:
-                    trace.append(("launch", bi, round((time.perf_counter() - t_run) * 1e3, 2)))
-                progressed = True
-            if len(gate) >= n_gate and active:
-                gate = []                    # (launches after the first ones: no gate)
-                n_gate = 0
-            for i in list(active):
-                bi, c, ev, flag, k = active[i]
-                if not ev.query():
+            if len(gate) >= n_gate:
+                launched = self._launch_waiting(waiting, n - nxt, gate)
+                active += launched
+                progressed = progressed or bool(launched)
+                if active:
+                    gate, n_gate = [], 0     # (launches after the first ones: no gate)
+            for r in list(active):
+                if not self._poll(r):
                     continue
                 progressed = True
-                p, s = self.pipes[i], self.streams[k]
-                if int(flag[1]) < 0:          # gave up (not co-resident): finish stepwise
-                    self.gave_up += 1
-                    with torch.cuda.stream(s):
-                        p.decoder.resume_stepwise()
-                        p.decoder.step_chunk(None)
-                        ev, flag = p.decoder.finished_async()
-                    slots.pop(i, None)
-                    active[i] = (bi, 1, ev, flag, k)
-                    continue
-                if int(flag[0]) or c >= p.decoder.n_chunks:
-                    p.decoder.note_persist_steps(int(flag[3]))
-                    self.decode_steps[bi] = int(flag[3])
-                    with torch.cuda.stream(s):
-                        results[bi] = _copy_batch(p.result(), caller)
-                        if keep is not None:
-                            keep(results[bi])
-                    del active[i]
-                    slots.pop(i, None)
-                    sbusy.discard(k)
-                    free.append(i)
-                else:
-                    with torch.cuda.stream(s):
-                        p.decoder.step_chunk(int(flag[2]))
-                        ev, flag = p.decoder.finished_async()
-                    active[i] = (bi, c + 1, ev, flag, k)
-            if progressed:
-                t_prog = time.perf_counter()
-            else:
-                time.sleep(20e-6)
-                if time.perf_counter() - t_prog > STALL_S:
-                    raise RuntimeError(
-                        f"ConcurrentRunner (begin_first): no progress for {STALL_S} s; begun "
-                        f"{begun}, active {[(i, a[0], a[1], a[4]) for i, a in active.items()]}, "
-                        f"grids {slots}, next batch {nxt} of {n}")
-        for s in self.streams:
-            caller.wait_stream(s)
-        if ahead is not None:
-            caller.wait_stream(self.enc_stream)
-        return results
+                if r.done:
+                    active.remove(r)
+                    free.append(r.owner)
+                    if n > len(self.pipes):      # (pipelines take further batches)
+                        copied[r.owner] = torch.cuda.Event()
+                        copied[r.owner].record(r.stream)
+            self._idle(progressed, waiting, active)
+        return self._finish(self.streams, ahead)
 
     def _run_grouped(self, batches, keep, inputs, caller):
         """run() with begin_first and begin_group k: one begin per group of k consecutive eval
@@ -870,18 +862,13 @@ class ConcurrentRunner:
         a stream no grid is running on, after its group's begin -- the first ones after every
         group's begin has finished on the GPU."""
         n, k, S = len(batches), self.begin_group, len(self.streams)
-        budget = self.budget
         groups = [list(range(g, min(n, g + k))) for g in range(0, n, k)]
         while len(self.gpipes) < len(groups):
             self.gpipes.append(self.pipes[0].group_twin(k))
-        results: List[Optional[CaptionBatch]] = [None] * n
-        self.decode_steps = [0] * n
-        self.assign, self.grid, self.gave_up = [], [0] * n, 0
-        gev = []
-        trace = self.trace = [] if os.environ.get("ZSAAC_RUNNER_TRACE") else None
-        if trace is not None:
-            self.traces = getattr(self, "traces", []) + [trace]
-        t_run = t_prog = time.perf_counter()
+        self._start(n, keep, caller, SlotAccount(self.grids, self.budget, S), "begin_group")
+        if self.trace is not None:       # (every run's: tools/sched_trace.py)
+            self.traces = getattr(self, "traces", []) + [self.trace]
+        gate = []           # every group's begin (gating on fewer brought the late grid back: r6w)
         for gi, bl in enumerate(groups):      # (on one stream: 5.3k instead of 7.3k clips/s)
             G, s = self.gpipes[gi], self.streams[gi % S]
             with torch.cuda.stream(s):
@@ -890,99 +877,34 @@ class ConcurrentRunner:
                               [int(batches[b].shape[0]) for b in bl])
                 ev = torch.cuda.Event()
                 ev.record(s)
-            gev.append(ev)
-            if trace is not None:
-                trace.append(("begin_group", gi, round((time.perf_counter() - t_run) * 1e3, 2)))
-        pending = [(gi, j, b) for gi, bl in enumerate(groups) for j, b in enumerate(bl)]
-        self.bdec = {b: self.gpipes[gi].subs[j] for gi, j, b in pending}
-        gate = list(gev)    # (gating on fewer groups brought the late grid back: r6w)
-        active, slots, sbusy = {}, {}, set()
-        while pending or active:
-            progressed = False
-            while pending and len(sbusy) < S:
-                gi, j, b = pending[0]
-                used = sum(slots.values())
-                g = choose_persist_grid(used, len(pending), self.grids, budget)
-                if used + g > budget:
-                    break
-                kk = next(q for q in range(S) if q not in sbusy)
-                d, s = self.gpipes[gi].subs[j], self.streams[kk]
-                d.persist_grid = g
-                d.persist_exclusive = False
-                with torch.cuda.stream(s):
-                    s.wait_event(gev[gi])
-                    for ev in gate:          # the first launches: after every group's begin
-                        s.wait_event(ev)
-                    if gate and STAGGER_US:      # the first wave's grids released in turn
-                        ops.stream_spin(STAGGER_US * len(sbusy), s)
-                    d.launch_pending()
-                    ev, flag = d.finished_async()
-                slots[b] = g
-                sbusy.add(kk)
-                self.grid[b] = g
-                self.assign.append((gi, b))
-                active[b] = (gi, j, 0, ev, flag, kk)
-                pending.pop(0)
-                if trace is not None:
-                    trace.append(("launch", b, round((time.perf_counter() - t_run) * 1e3, 2)))
-                progressed = True
+            gate.append(ev)
+            self._note("begin_group", gi)
+        waiting = [_InFlight(G.subs[j], lambda G=G, j=j: G.sub_result(j), b, gi, begun=gate[gi])
+                   for gi, (G, bl) in enumerate(zip(self.gpipes, groups)) for j, b in enumerate(bl)]
+        self.bdec = {r.batch: r.dec for r in waiting}
+        active = []
+        while waiting or active:
+            launched = self._launch_waiting(waiting, 0, gate)
+            self.assign += [(r.owner, r.batch) for r in launched]
+            active += launched
+            progressed = bool(launched)
             if active:
                 gate = []
-            for b in list(active):
-                gi, j, c, ev, flag, kk = active[b]
-                if not ev.query():
-                    continue
-                progressed = True
-                G, s = self.gpipes[gi], self.streams[kk]
-                d = G.subs[j]
-                if int(flag[1]) < 0:          # gave up (not co-resident): finish stepwise
-                    self.gave_up += 1
-                    with torch.cuda.stream(s):
-                        d.resume_stepwise()
-                        d.step_chunk(None)
-                        ev, flag = d.finished_async()
-                    slots.pop(b, None)
-                    active[b] = (gi, j, 1, ev, flag, kk)
-                    continue
-                if int(flag[0]) or c >= d.n_chunks:
-                    d.note_persist_steps(int(flag[3]))
-                    self.decode_steps[b] = int(flag[3])
-                    if trace is not None:
-                        trace.append(("done", b, round((time.perf_counter() - t_run) * 1e3, 2)))
-                    with torch.cuda.stream(s):
-                        results[b] = _copy_batch(G.sub_result(j), caller)
-                        if keep is not None:
-                            keep(results[b])
-                    del active[b]
-                    slots.pop(b, None)
-                    sbusy.discard(kk)
-                else:
-                    with torch.cuda.stream(s):
-                        d.step_chunk(int(flag[2]))
-                        ev, flag = d.finished_async()
-                    active[b] = (gi, j, c + 1, ev, flag, kk)
-            if progressed:
-                t_prog = time.perf_counter()
-            else:
-                time.sleep(20e-6)
-                if time.perf_counter() - t_prog > STALL_S:
-                    raise RuntimeError(
-                        f"ConcurrentRunner (begin_group): no progress for {STALL_S} s; pending "
-                        f"{pending[:4]}.., active {[(b, a[0], a[2], a[5]) for b, a in active.items()]}, "
-                        f"grids {slots}")
-        for s in self.streams:
-            caller.wait_stream(s)
-        return results
-
-    def _encode_ahead(self, batches, caller):
-        """The encoder passes of every batch on the encoder stream: consecutive batches grouped
-        up to encode_ahead clips (one view when they are adjacent rows of one tensor, as the
-        bench's are, else concatenated), enqueued one pass at a time (_EncodeAhead.pump): a pass
-        queued far ahead would hold the GPU ahead of the begins issued after it."""
-        return _EncodeAhead(self, batches, caller)
+            for r in list(active):
+                if self._poll(r):
+                    progressed = True
+                    if r.done:
+                        active.remove(r)
+            self._idle(progressed, waiting, active)
+        return self._finish(self.streams)
 
 
 class _EncodeAhead:
+    """The encoder passes of every batch on the runner's encoder stream: consecutive batches
+    grouped up to encode_ahead clips (one view when they are adjacent rows of one tensor, as the
+    bench's are, else concatenated), enqueued one pass at a time (pump): a pass queued far ahead
+    would hold the GPU ahead of the begins issued after it."""
+
     def __init__(self, runner, batches, caller):
         E = runner.encode_ahead
         self.enc, self.es, self.batches = runner.enc, runner.enc_stream, batches
@@ -1004,8 +926,6 @@ class _EncodeAhead:
                 c0 += int(b.shape[0])
             i = j
         self.events = []
-        self.graph = runner.enc_graph
-        self.first = runner.encode_first
         self.pump(force=1)
 
     def pump(self, force=0):
@@ -1015,15 +935,16 @@ class _EncodeAhead:
                 return
             i, j, c0, m = self.passes[len(self.events)]
             with torch.cuda.stream(self.es):
-                enc = self.enc.encode_graphed if self.graph else self.enc.encode
-                self.emb[c0:c0 + m].copy_(enc(_rows_span(self.batches[i:j])))
+                # (replayed from per-size hipGraphs, Encoder.encode_graphed: within the noise
+                # of kernel-by-kernel enqueue, the A/B among profiles/r5/headline_ab_*.txt)
+                self.emb[c0:c0 + m].copy_(self.enc.encode_graphed(_rows_span(self.batches[i:j])))
                 ev = torch.cuda.Event()
                 ev.record(self.es)
             self.events.append(ev)
 
     def ready(self, b):
         """The event batch b's begin waits for (its pass enqueued first if needed)."""
-        k = len(self.passes) - 1 if self.first else self.pass_of[b]
+        k = self.pass_of[b]
         self.pump(force=k + 1)
         return self.events[k]
 

@@ -13,7 +13,7 @@ condition on (predict_prompt.py:129-148), not on the padded training layout:
     [wte(hard) ; soft ; wte(cap[:T_b - 1])]      positions 0 .. S_b - 1
 
 token ``cap[b][t]`` being predicted from the row at position ``H_b + n - 1 + t``; temperature 1.
-Per call: prompt assembly and mapper (as CaptionPipeline._begin_device), zs_gpt2_score_embed,
+Per call: prompt assembly and mapper (as CaptionPipeline.begin_emb), zs_gpt2_score_embed,
 the decoder's ragged prefill, ln_f of the scored rows only, zs_lmhead_nll (the LM head with the
 softmax statistics and the target's logit taken in registers: no [rows, 50257] logits in memory)
 and zs_nll_finalize.  Nothing synchronises with the host until a result is read.
