@@ -82,6 +82,30 @@ int zs_wav2img(const float* in, int B, int T_in, float* img, void* stream);
 int zs_pack_clips(const float* flat, const long* offsets, const int* lengths, int B, int T,
                   float* out, void* stream);
 
+/* zs_resample_pack: data_handing/embeddings_generator.py:48-59 from decoded files --
+ * librosa.load(path, sr=sr_out, mono=True) and the crop / pad to T -- in one launch per 64 clips:
+ * clip b is n_frames[b] interleaved frames of channels[b] channels at sr_in[b] Hz, starting at
+ * element offsets[b] of the flat device buffer `frames` (fmt 0: f32, 1: s16, read as x / 32768).
+ * out [B][T] f32: row b is librosa.to_mono (np.mean over the channels, f32) resampled with
+ * resampy's resample_f to sr_out (librosa 0.9.2's res_type "kaiser_best"), its first
+ * min(n_out[b], T) outputs; every later element of the row is 0.  n_out[b] is resampy's output
+ * length int(n_frames * (sr_out / sr_in)) of the WHOLE file, so n_frames[b] may be a prefix of it
+ * (the first T outputs read ceil(T sr_in / sr_out) + wing + 1 frames).  sr_in[b] == sr_out is
+ * the downmix alone, bit-exact (librosa does not resample then).
+ * table [num_zeros << precision | 1][2] f32 on the device, 8-byte aligned: (win[i], win[i+1] -
+ * win[i]) of resampy's half filter, the last delta 0; kaiser_best is num_zeros 64, precision 9.
+ * Output t sits at input time t sr_in / sr_out, held as the 64-bit integer quotient and
+ * remainder of t * sr_in by sr_out (exact at any t).
+ * offsets, n_frames, channels, sr_in and n_out are HOST arrays [B] (they are validated here and
+ * travel as kernel arguments: no copy, no synchronisation).  Accepts B > 0, T > 0, fmt 0 | 1,
+ * 1 <= channels <= 8, 1 <= sr <= 2^24, sr_in <= 8 sr_out, sr_out <= 8 sr_in, a table step
+ * int(min(1, sr_out / sr_in) << precision) >= 1, non-NULL pointers; anything else is refused
+ * before the first launch. */
+int zs_resample_pack(const void* frames, int fmt, const long* offsets, const int* n_frames,
+                     const int* channels, const int* sr_in, const int* n_out, int B, int sr_out,
+                     int T, const float* table, int num_zeros, int precision, float* out,
+                     void* stream);
+
 /* zs_patch_embed: htsat.py:115-125 PatchEmbed (Conv2d 1->96, k4 s4) + LayerNorm(96):
  * img [B][256][256] f32 -> x [B*4096][96] f32 (token = row*64 + col of the 64x64 patch grid).
  * Accepts 0 < B <= 32767; non-NULL buffers. */

@@ -530,9 +530,233 @@ __global__ __launch_bounds__(256) void pack_clips_kernel(const float* __restrict
   }
 }
 
+// ------------------------------------------------------------------ resample + downmix + pack
+// librosa.load(path, sr, mono=True) followed by the crop / pad of
+// data_handing/embeddings_generator.py:48-59, for clips that arrive as decoded, interleaved
+// frames at their files' own rates: to_mono (np.mean over the channels, f32), resampy's
+// resample_f with the kaiser_best table (librosa 0.9.2's default res_type), the first T outputs
+// kept and the rest of the row zero.
+//
+// One 256-thread block per RS_TILE consecutive outputs of one clip.  The tile's input span
+// (the samples between its first output's left wing and its last output's right wing) is
+// downmixed once into LDS; each lane then accumulates four of the tile's outputs in a register,
+// reading (win, delta) pairs of the interleaved table from global memory (256 KB, resident in
+// L2; which output a lane takes is chosen so that a wave's lanes read neighbouring phases:
+// rs_stride).
+//
+// Time base: output t sits at input time t * sr_in / sr_out.  p = t * sr_in is a 64-bit integer,
+// n = p / sr_out the sample left of it and r = p % sr_out the exact remainder, so the table
+// phase frac * nb = scale * nb * r / sr_out = nb * r / max(sr_in, sr_out) is an integer quotient
+// (the table offset) and an integer remainder (eta's numerator): no rounding until eta itself,
+// and no dependence between outputs (resampy adds 1/ratio into a float64 register per output).
+constexpr int RS_TILE = 1024;             // outputs per block (4 per lane)
+constexpr int RS_MAX_CLIPS = 64;          // clips per launch (their descriptors are kernel arguments)
+constexpr int RS_MAX_CH = 8;
+
+struct RsClip {
+  long off;        // first sample of the clip in the flat buffer
+  int n_frames;    // frames present
+  int channels;
+  int sr_in;
+  int n_valid;     // min(n_out, T): outputs computed, the rest of the row is zero
+  int step;        // table stride per input sample: int(scale * nb)
+  int wing;        // most taps of one wing: (nwin - 1) / step + 1
+  int stride;      // odd: lane j of a tile takes output (j * stride) mod RS_TILE (rs_stride)
+  int pad_;
+};
+struct RsBatch { RsClip c[RS_MAX_CLIPS]; };
+
+// The odd stride q < RS_TILE whose step in table phase, q * sr_in mod sr_out, is circularly the
+// smallest non-zero one (1 when every output has the same phase): consecutive lanes then read
+// neighbouring table entries.  44.1 -> 32 kHz: q = 119 moves the phase by 1 / 320 of a sample,
+// so the 64 lanes of a wave read within a fifth of one table step instead of all over it.
+inline int rs_stride(int sr_in, int sr_out) {
+  int best = 1;
+  long bestd = -1;
+  for (int q = 1; q < RS_TILE; q += 2) {
+    const long m = (long)q * sr_in % sr_out;
+    const long d = std::min(m, (long)sr_out - m);
+    if (d > 0 && (bestd < 0 || d < bestd)) { bestd = d; best = q; }
+  }
+  return best;
+}
+
+template <bool S16>
+__device__ __forceinline__ float rs_sample(const void* frames, long i) {
+  if (S16) return (float)static_cast<const short*>(frames)[i] * (1.0f / 32768.0f);   // exact
+  return static_cast<const float*>(frames)[i];
+}
+
+// np.mean over the C channels of one frame as numpy sums them in float32: in order for C < 8,
+// the 8-accumulator pairwise tree for C == 8; then one division by C.
+template <bool S16>
+__device__ __forceinline__ float rs_downmix(const void* frames, long base, int C) {
+  if (C == 1) return rs_sample<S16>(frames, base);
+  float s;
+  if (C == RS_MAX_CH) {
+    float v[RS_MAX_CH];
+#pragma unroll
+    for (int c = 0; c < RS_MAX_CH; ++c) v[c] = rs_sample<S16>(frames, base + c);
+    s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+  } else {
+    s = rs_sample<S16>(frames, base);
+    for (int c = 1; c < C; ++c) s += rs_sample<S16>(frames, base + c);
+  }
+  return __fdiv_rn(s, (float)C);
+}
+
+// One wing of the filter: sum over i < count of (win + eta * delta)[i * step] * x[DIR * i], in
+// four interleaved partial sums (independent FMA chains; the rounding error of the sum stays
+// well below that of one float32 chain over the same taps).
+template <int DIR>
+__device__ __forceinline__ float rs_wing(const float2* __restrict__ tp, int step, float eta,
+                                         const float* x, int count) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int i = 0;
+  for (; i + 4 <= count; i += 4) {
+    const float2 w0 = tp[(long)i * step], w1 = tp[(long)(i + 1) * step];
+    const float2 w2 = tp[(long)(i + 2) * step], w3 = tp[(long)(i + 3) * step];
+    a0 = fmaf(fmaf(eta, w0.y, w0.x), x[DIR * i], a0);
+    a1 = fmaf(fmaf(eta, w1.y, w1.x), x[DIR * (i + 1)], a1);
+    a2 = fmaf(fmaf(eta, w2.y, w2.x), x[DIR * (i + 2)], a2);
+    a3 = fmaf(fmaf(eta, w3.y, w3.x), x[DIR * (i + 3)], a3);
+  }
+  for (; i < count; ++i) {
+    const float2 w0 = tp[(long)i * step];
+    a0 = fmaf(fmaf(eta, w0.y, w0.x), x[DIR * i], a0);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+template <bool S16>
+__global__ __launch_bounds__(256) void resample_pack_kernel(
+    const void* __restrict__ frames, const RsBatch batch, int b0, int sr_out, int T,
+    const float2* __restrict__ table, int nwin, int nb, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float rs_x[];
+  const RsClip& cl = batch.c[blockIdx.y];
+  const long off = cl.off;
+  const int n_frames = cl.n_frames, C = cl.channels, sr_in = cl.sr_in, n_valid = cl.n_valid;
+  float* row = out + (long)(b0 + blockIdx.y) * T;
+  const int t0 = blockIdx.x * RS_TILE;
+  const int t1 = min(t0 + RS_TILE, T);
+  const int tv = min(t1, n_valid);         // outputs [t0, tv) are computed, [tv, t1) are zero
+  if (tv <= t0) {
+    for (int t = t0 + threadIdx.x; t < t1; t += 256) row[t] = 0.f;
+    return;
+  }
+  if (sr_in == sr_out) {                   // librosa does not resample: the downmix alone
+    for (int t = t0 + threadIdx.x; t < t1; t += 256)
+      row[t] = (t < tv && t < n_frames) ? rs_downmix<S16>(frames, off + (long)t * C, C) : 0.f;
+    return;
+  }
+  const int step = cl.step, W = cl.wing;
+  const int n_lo = (int)((long)t0 * sr_in / sr_out);
+  const int n_hi = (int)((long)(tv - 1) * sr_in / sr_out);
+  const int s0 = n_lo - W + 1;             // input sample held by rs_x[0]
+  const int span = n_hi - n_lo + 2 * W;    // host: span <= the launch's LDS floats
+  for (int i = threadIdx.x; i < span; i += 256) {
+    const int m = s0 + i;
+    rs_x[i] = (m >= 0 && m < n_frames) ? rs_downmix<S16>(frames, off + (long)m * C, C) : 0.f;
+  }
+  __syncthreads();
+  const int D = max(sr_in, sr_out);
+  const float inv_d = 1.0f / (float)D;
+  const float gain = sr_out < sr_in ? (float)((double)sr_out / (double)sr_in) : 1.0f;
+  // lane j takes output t0 + (j * stride mod RS_TILE): an odd stride permutes the tile, and the
+  // host picks the one that puts outputs of neighbouring table phase into neighbouring lanes
+  const int stride = cl.stride;
+  for (int j = threadIdx.x; j < RS_TILE; j += 256) {
+    const int t = t0 + ((j * stride) & (RS_TILE - 1));
+    if (t >= t1) continue;
+    float y = 0.f;
+    if (t < tv) {
+      const long p = (long)t * sr_in;
+      const int n = (int)(p / sr_out), r = (int)(p % sr_out);
+      const float* xc = rs_x + (n - s0);   // x[n]
+      {                                    // left wing: x[n - i]
+        const long ph = (long)nb * r;
+        const int o = (int)(ph / D);
+        const float eta = (float)(int)(ph % D) * inv_d;
+        const int imax = min(n + 1, (nwin - o) / step);
+        y = rs_wing<-1>(table + o, step, eta, xc, imax);
+      }
+      {                                    // right wing: x[n + 1 + k]
+        const long ph = (long)nb * (sr_out - r);
+        const int o = (int)(ph / D);
+        const float eta = (float)(int)(ph % D) * inv_d;
+        const int kmax = min(n_frames - n - 1, (nwin - o) / step);
+        y += rs_wing<1>(table + o, step, eta, xc + 1, kmax);
+      }
+      y *= gain;
+    }
+    row[t] = y;
+  }
+}
+
 }  // namespace zs
 
 using namespace zs;
+
+extern "C" int zs_resample_pack(const void* frames, int fmt, const long* offsets,
+                                const int* n_frames, const int* channels, const int* sr_in,
+                                const int* n_out, int B, int sr_out, int T, const float* table,
+                                int num_zeros, int precision, float* out, void* stream) {
+  ZS_REQUIRE(frames && offsets && n_frames && channels && sr_in && n_out && table && out,
+             "zs_resample_pack: NULL buffer");
+  ZS_REQUIRE(B > 0 && T > 0, "zs_resample_pack: B > 0, T > 0");
+  ZS_REQUIRE(fmt == 0 || fmt == 1, "zs_resample_pack: fmt %d (0: f32, 1: s16)", fmt);
+  ZS_REQUIRE(sr_out >= 1 && sr_out <= (1 << 24), "zs_resample_pack: 1 <= sr_out <= 2^24");
+  ZS_REQUIRE(num_zeros >= 1 && num_zeros <= 1024 && precision >= 0 && precision <= 12,
+             "zs_resample_pack: 1 <= num_zeros <= 1024, 0 <= precision <= 12");
+  ZS_REQUIRE(((uintptr_t)table & 7) == 0, "zs_resample_pack: table 8-byte aligned");
+  const int nb = 1 << precision, nwin = nb * num_zeros + 1;
+  // every clip is checked before the first launch
+  for (int b = 0; b < B; ++b) {
+    ZS_REQUIRE(channels[b] >= 1 && channels[b] <= RS_MAX_CH,
+               "zs_resample_pack: clip %d has %d channels (1..%d)", b, channels[b], RS_MAX_CH);
+    ZS_REQUIRE(sr_in[b] >= 1 && sr_in[b] <= (1 << 24), "zs_resample_pack: clip %d: 1 <= sr_in <= 2^24", b);
+    ZS_REQUIRE((long)sr_in[b] <= 8L * sr_out && (long)sr_out <= 8L * sr_in[b],
+               "zs_resample_pack: clip %d: %d Hz -> %d Hz is beyond a factor of 8", b, sr_in[b], sr_out);
+    ZS_REQUIRE(n_frames[b] >= 0 && n_out[b] >= 0 && offsets[b] >= 0,
+               "zs_resample_pack: clip %d: negative length or offset", b);
+    ZS_REQUIRE((long)T * sr_in[b] / sr_out < 0x7fffffffL,
+               "zs_resample_pack: clip %d: T * sr_in / sr_out does not fit an int", b);
+    const int step = sr_out < sr_in[b] ? (int)((long)nb * sr_out / sr_in[b]) : nb;
+    ZS_REQUIRE(step >= 1, "zs_resample_pack: clip %d: table step 0 (precision %d too low for %d Hz -> %d Hz)",
+               b, precision, sr_in[b], sr_out);
+    const long span = (long)(RS_TILE - 1) * sr_in[b] / sr_out + 2L * ((nwin - 1) / step + 1) + 2;
+    ZS_REQUIRE(span * 4 <= 65536, "zs_resample_pack: clip %d: a tile's input span (%ld floats) exceeds 64 KB of LDS", b, span);
+  }
+  for (int b0 = 0; b0 < B; b0 += RS_MAX_CLIPS) {
+    const int nc = std::min(RS_MAX_CLIPS, B - b0);
+    RsBatch batch = {};
+    long lds = 0;
+    for (int j = 0; j < nc; ++j) {
+      const int b = b0 + j;
+      RsClip& c = batch.c[j];
+      c.off = offsets[b];
+      c.n_frames = n_frames[b];
+      c.channels = channels[b];
+      c.sr_in = sr_in[b];
+      c.n_valid = std::min(n_out[b], T);
+      c.step = sr_out < sr_in[b] ? (int)((long)nb * sr_out / sr_in[b]) : nb;
+      c.wing = (nwin - 1) / c.step + 1;
+      c.stride = rs_stride(sr_in[b], sr_out);
+      if (sr_in[b] != sr_out)
+        lds = std::max(lds, (long)(RS_TILE - 1) * sr_in[b] / sr_out + 2L * c.wing + 2);
+    }
+    const dim3 grid(cdiv(T, RS_TILE), nc);
+    const float2* tab = reinterpret_cast<const float2*>(table);
+    if (fmt == 1)
+      hipLaunchKernelGGL(resample_pack_kernel<true>, grid, dim3(256), lds * sizeof(float), S(stream),
+                         frames, batch, b0, sr_out, T, tab, nwin, nb, out);
+    else
+      hipLaunchKernelGGL(resample_pack_kernel<false>, grid, dim3(256), lds * sizeof(float), S(stream),
+                         frames, batch, b0, sr_out, T, tab, nwin, nb, out);
+    ZS_LAUNCH_CHECK();
+  }
+  return 0;
+}
 
 extern "C" int zs_pack_clips(const float* flat, const long* offsets, const int* lengths, int B,
                              int T, float* out, void* stream) {

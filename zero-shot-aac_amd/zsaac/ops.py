@@ -70,6 +70,35 @@ def pack_clips(flat, offsets, lengths, T, out):
     return out[:B]
 
 
+def resample_pack(frames, offsets, n_frames, channels, sr_in, n_out, sr_out, T, table, num_zeros,
+                  precision, out):
+    """Decoded clips -> out [B, T] at ``sr_out``: mono mean, resampy ``kaiser_best`` resampling,
+    crop / zero-pad (zs_resample_pack).  ``frames``: one flat device buffer, float32 or int16, of
+    interleaved frames; clip b is ``n_frames[b]`` frames of ``channels[b]`` channels at
+    ``sr_in[b]`` Hz from element ``offsets[b]``; ``n_out[b]`` its output length before the crop
+    (``audio_io.resample_plan``).  The five per-clip sequences live on the host.  ``table``: the
+    device copy of ``audio_io.resample_filter``'s table."""
+    import numpy as np
+    _need(frames.dtype in (torch.float32, torch.int16) and frames.is_contiguous(),
+          "resample_pack: frames float32 or int16, contiguous")
+    _need(table.dtype == torch.float32 and table.is_contiguous()
+          and table.numel() == 2 * ((num_zeros << precision) + 1),
+          "resample_pack: table [(num_zeros << precision) + 1, 2] float32")
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    meta = [np.ascontiguousarray(a, dtype=np.int32) for a in (n_frames, channels, sr_in, n_out)]
+    B = off.shape[0]
+    _need(B > 0 and all(a.shape == (B,) for a in meta), "resample_pack: five sequences of length B")
+    _need(out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= B
+          and out.shape[1] == T, "resample_pack: out [B, T] float32")
+    end = off + meta[0].astype(np.int64) * meta[1]
+    _need(bool((off >= 0).all()) and bool((meta[0] >= 0).all()) and int(end.max()) <= frames.numel(),
+          "resample_pack: a clip lies outside the frame buffer")
+    call("zs_resample_pack", _p(frames), 1 if frames.dtype == torch.int16 else 0, off.ctypes.data,
+         *[a.ctypes.data for a in meta], B, int(sr_out), T, _p(table), num_zeros, precision,
+         _p(out), _s())
+    return out[:B]
+
+
 def wav2img(logmel_t, out=None):
     B, T_in, F = logmel_t.shape
     _need(F == 64, "wav2img expects 64 mel bins")
