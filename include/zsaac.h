@@ -594,6 +594,47 @@ int zs_sim_rank(int M, int N, int K, int dtype, const void* Q, int ldq, const vo
 int zs_sim_topk_finalize(const float* part_val, const int* part_idx, int M, int nblk, int kpart,
                          int k, float* out_val, int* out_idx, void* stream);
 
+/* ------------------------------------------------------------------ text memory bank
+ * map2memory (predict_prompt.py:23-29): an embedding is replaced by the softmax-weighted mix of a
+ * bank of caption embeddings, `softmax(100 * q @ T.T) @ T`, normalised.  Queries Q [M][ldq], bank
+ * [N][ldb] (dtype f32 or bf16, rows as stored), float scale:
+ *   z[m][n] = scale * (Q[m] . bank[n])           dots accumulated in f32
+ *   lse[m]  = log sum_n exp(z[m][n])
+ *   mix[m]  = sum_n exp(z[m][n] - lse[m]) bank[n]                      f32 [M][K]
+ * One streaming pass with an online softmax: no [M][N] array exists, every bank tile is fetched
+ * once and serves both products.  bf16: bf16 MFMA, f32 accumulation, the softmax weights rounded
+ * to bf16 for the second product and the running sum adding the rounded values; f32: exact f32
+ * products (v_mfma_f32_32x32x2_f32).  No atomics; a row's result does not depend on M or on the
+ * rows that share the launch, and is bit-identical from run to run.
+ *
+ * zs_memory_nsplit (predict_prompt.py:23-29): the default number of bank splits, a function of
+ *   (N, K, dtype) only; -1 for arguments zs_memory_project refuses. */
+int zs_memory_nsplit(int N, int K, int dtype);
+
+/* zs_memory_project (predict_prompt.py:23-29): the bank rows are cut into nsplit contiguous
+ *   splits (flash-decoding); split s writes, per row m, part_mix[m][s][0..K) = a =
+ *   sum_n exp(z - m_s) bank[n], and part_ml[m][s] = (m_s, l_s) = (max z, sum exp(z - m_s)) over
+ *   its rows; a split with no rows (nsplit larger than the number of tiles) writes (0, -inf, 0).
+ *   part_mix [M][nsplit][K] f32, part_ml [M][nsplit][2] f32.
+ *   Accepts: M, N > 0; K % 32 == 0, 32 <= K <= 1024; ldq / ldb % 8 == 0 and >= K (padding
+ *   columns are never read); 1 <= nsplit <= 4096; Q, bank, part_mix 16-byte aligned; no NULL.
+ *   Everything else is refused (-1 and a message) before any launch, outputs untouched. */
+int zs_memory_project(int M, int N, int K, int dtype, const void* Q, int ldq, const void* bank,
+                      int ldb, float scale, int nsplit, float* part_mix, float* part_ml,
+                      void* stream);
+
+/* zs_memory_merge (predict_prompt.py:23-29): merges the partials in split order:
+ *   m* = max_s m_s, L = sum_s l_s e^(m_s - m*), mix = sum_s a_s e^(m_s - m*) / L,
+ *   lse = m* + log L; an empty split (0, -inf, 0) contributes nothing (no NaN).
+ *   normalize != 0: out[m] = mix[m] / max(||mix[m]||, 1e-12) (the eps convention of
+ *   zs_l2norm_rows; the reference divides by the bare norm), else out[m] = mix[m].
+ *   out [M][ldo] f32, lse [M] f32 or NULL.  A finished chunk re-enters a later merge as
+ *   (mix, lse, 1): banks larger than one tensor, or sharded, are combined this way.
+ *   Accepts: M > 0, 1 <= nsplit <= 4096, K as above, ldo % 8 == 0 and >= K, part_mix and out
+ *   16-byte aligned, no NULL except lse; everything else is refused before the launch. */
+int zs_memory_merge(const float* part_mix, const float* part_ml, int M, int nsplit, int K,
+                    int normalize, float* out, int ldo, float* lse, void* stream);
+
 /* zs_prefix_ids_assemble: get_prefix_tokens (gpt2_prefix_eval.py:271-278) with the argmax run
  * only over the soft-prompt rows: out[b][p] = hard_ids[b][p] for p < hard_len[b] (a hard row is
  * wte[id] and its own cosine is the maximum — the caller verifies that every possible hard id

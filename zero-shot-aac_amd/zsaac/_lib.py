@@ -77,6 +77,9 @@ SIGNATURES = {
     "zs_nll_finalize": [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P],
     "zs_sim_rank": [I, I, I, I, P, I, P, I, P, I, P, P, P],
     "zs_sim_topk_finalize": [P, P, I, I, I, I, P, P, P],
+    "zs_memory_nsplit": [I, I, I],
+    "zs_memory_project": [I, I, I, I, P, I, P, I, F, I, P, P, P],
+    "zs_memory_merge": [P, P, I, I, I, I, P, I, P, P],
     "zs_prefix_ids_assemble": [P, I, P, P, I, I, I, P, P],
     "zs_greedy_step": [P, P, I, I, P, I, I, I, P, P, P, P, P, P, P],
     "zs_greedy_init": [I, P, P, P, P, P, I, P, P, P],

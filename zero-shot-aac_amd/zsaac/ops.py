@@ -538,6 +538,41 @@ def sim_topk_finalize(part_val, part_idx, M, nblk, kpart, k, out_val, out_idx):
          _p(out_idx), _s())
 
 
+# ---------------------------------------------------------------- text memory bank
+def memory_nsplit(N, K, dtype):
+    """zs_memory_nsplit: the default split count of a bank of N rows (never a function of M)."""
+    return call("zs_memory_nsplit", N, K, dt(dtype))
+
+
+def memory_project(q, bank, scale, nsplit, part_mix, part_ml, M=None):
+    """zs_memory_project: one streaming pass of q [M, K] over bank [N, K] (softmax(scale q B^T) B
+    with an online softmax), as nsplit partials part_mix [M, nsplit, K] / part_ml [M, nsplit, 2]."""
+    _need(q.dim() == 2 and bank.dim() == 2, "memory_project: q and bank are 2-D")
+    K = q.shape[1]
+    M = M if M is not None else q.shape[0]
+    _need(q.dtype == bank.dtype and bank.shape[1] == K and q.stride(1) == 1
+          and bank.stride(1) == 1 and q.shape[0] >= M, "memory_project: dtype/shape mismatch")
+    _need(part_mix.dtype == part_ml.dtype == torch.float32 and part_mix.is_contiguous()
+          and part_ml.is_contiguous() and nsplit >= 1 and part_mix.numel() >= M * nsplit * K
+          and part_ml.numel() >= M * nsplit * 2, "memory_project: buffer sizes")
+    call("zs_memory_project", M, bank.shape[0], K, dt(q), _p(q), q.stride(0), _p(bank),
+         bank.stride(0), float(scale), nsplit, _p(part_mix), _p(part_ml), _s())
+
+
+def memory_merge(part_mix, part_ml, M, nsplit, K, out, normalize=True, lse=None):
+    """zs_memory_merge: the partials of zs_memory_project (or finished chunks as (mix, lse, 1))
+    -> out [M, K] f32 (rows of stride out.stride(0)), optionally L2-normalised, and lse [M]."""
+    _need(part_mix.dtype == part_ml.dtype == out.dtype == torch.float32
+          and part_mix.is_contiguous() and part_ml.is_contiguous() and out.dim() == 2
+          and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= K
+          and part_mix.numel() >= M * nsplit * K and part_ml.numel() >= M * nsplit * 2,
+          "memory_merge: buffers")
+    _need(lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= M),
+          "memory_merge: lse is [M] f32")
+    call("zs_memory_merge", _p(part_mix), _p(part_ml), M, nsplit, K, int(bool(normalize)), _p(out),
+         out.stride(0), _p(lse), _s())
+
+
 def prefix_ids_assemble(hard_ids, hard_len, soft_idx, n_soft, B, Pmax, out):
     _i32(hard_ids, "hard_ids"), _i32(hard_len, "hard_len"), _i32(soft_idx, "soft_idx"), _i32(out, "out")
     call("zs_prefix_ids_assemble", _p(hard_ids), hard_ids.shape[-1], _p(hard_len), _p(soft_idx),

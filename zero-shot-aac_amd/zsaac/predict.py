@@ -22,6 +22,9 @@ but ``nll.txt``, the teacher-forced NLL of the pickle's reference captions (zsaa
 checkpoint
 (``--clap``, the reference's HTSAT-BERT-ZS.pt: ``{"model": ASE state dict}``) supplies the BERT
 text tower and ``--bert_vocab`` its WordPiece vocabulary (bert-base-uncased's vocab.txt).
+``--memory PKL [PKL ...]`` projects every audio embedding onto the text memory bank built from
+those pickles before captioning (``map2memory`` / ``construct_support_memory``,
+predict_prompt.py:23-56; zsaac.memory), with softmax scale ``--memory_scale`` (default 100).
 """
 from __future__ import annotations
 
@@ -129,10 +132,13 @@ def build_pipeline(test_dir: str, params: Dict, tokenizer, isbeam: bool = False,
     return CaptionPipeline(sd, None, table, ltok, cfg, device=device), names
 
 
-def make_preds(pipe: CaptionPipeline, tokenizer, all_data: List[Dict],
+def make_preds(pipe: CaptionPipeline, tokenizer, all_data: List[Dict], memory=None,
+               memory_scale: float = 100.0,
                ) -> Tuple[Dict[str, List[str]], Dict[str, List[str]], Dict[str, List[str]]]:
     """predict_prompt.py:104-153 over batches of ``pipe.cfg.batch`` clips: returns key2pred
-    (lower-cased captions), key2pred_prefix (get_prefix_tokens strings) and key2refs."""
+    (lower-cased captions), key2pred_prefix (get_prefix_tokens strings) and key2refs.
+    ``memory`` (a zsaac.memory.SupportMemory): every batch's embeddings are projected onto the
+    text memory bank first (map2memory, predict_prompt.py:23-29)."""
     key2refs: Dict[str, List[str]] = {}
     for it in all_data:
         key2refs[it["audio_id"]] = post_processing(it.get("caption", []))
@@ -142,6 +148,8 @@ def make_preds(pipe: CaptionPipeline, tokenizer, all_data: List[Dict],
     for c0 in range(0, len(all_data), B):
         chunk = all_data[c0:c0 + B]
         emb = safeload.stack_rows([it["audio_embedding"] for it in chunk]).to(pipe.dev)
+        if memory is not None:
+            emb = memory.project(emb, scale=memory_scale)
         out = pipe.caption_emb(emb)
         caps = out.captions()                    # greedy: generated ids; beam: best beam
         prefs = out.prefix_token_lists()
@@ -284,7 +292,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--bert_vocab", type=str, default=None, help="--magic: BERT vocab.txt")
     ap.add_argument("--score", action="store_true",
                     help="score the pickle's reference captions instead of generating: nll.txt")
+    ap.add_argument("--memory", type=str, nargs="+", default=None, metavar="PKL",
+                    help="text-embedding pickles: project every audio embedding onto this memory "
+                         "bank before captioning (map2memory, predict_prompt.py:23-56)")
+    ap.add_argument("--memory_scale", type=float, default=100.0,
+                    help="--memory: the softmax scale (the reference's 100)")
     args = ap.parse_args(argv)
+    if args.memory and (args.magic or args.score):
+        ap.error("--memory cannot be combined with --magic or --score")
     if args.magic and not (args.clap and args.bert_vocab):
         raise SystemExit("--magic needs --clap <checkpoint> and --bert_vocab <vocab.txt>")
     params = load_params(args.test_dir)
@@ -311,7 +326,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         key2pred, key2pred_prefix, key2refs = make_preds_magic(
             pipe, tokenizer, all_data, clap_sd, bert_tok, width=width, alpha=alpha, beta=beta)
     else:
-        key2pred, key2pred_prefix, key2refs = make_preds(pipe, tokenizer, all_data)
+        memory = None
+        if args.memory:
+            from .memory import SupportMemory, construct_support_memory
+            memory = SupportMemory(construct_support_memory(args.memory), dtype=dtype, device=pipe.dev)
+        key2pred, key2pred_prefix, key2refs = make_preds(pipe, tokenizer, all_data, memory,
+                                                         args.memory_scale)
     write_outputs(args.test_dir, key2pred, key2pred_prefix, key2refs)
     return 0
 
