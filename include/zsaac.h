@@ -668,6 +668,33 @@ int zs_greedy_step_map(const float* part_val, const int* part_idx, int R, const 
                        int* out_ids, int* out_len, int* done, int* pos, int* next_tok,
                        int* all_done, void* stream);
 
+/* zs_sample_rows: one sampled token per row of f32 logits [R][ld] (generate2's `top_p` /
+ * `temperature`, gpt2_prefix_eval.py:161-222; the nucleus rule of its lines 197-206), in HF's
+ * processor order:
+ *   z = logits / temperature;
+ *   top_k > 0: keep the min(top_k, V) largest z, ties at the cut to the lower id; probabilities
+ *     from here on are renormalised over what is kept;
+ *   top_p < 1: order the kept tokens by p descending (ties: lower id first) and keep rank i iff
+ *     the mass strictly before it is <= top_p (rank 0 always);
+ *   draw: in increasing id order, the first kept token whose running kept mass exceeds
+ *     u * kept mass, u = (w + 0.5) * 2^-32, w = the first output word of Philox4x32-10 with the
+ *     64-bit `seed` as key and the counter (row_id[r], *step_ctr, 0, 0) -- row_id NULL: r.  The
+ *     step is read on the device (as zs_greedy_step reads it, which then advances it), and a
+ *     row's draw depends on its id, not on its slot in the launch.
+ * part_val[r] = logits[r][tok], part_idx[r] = tok: the [R][1][1] partials of an nblk = 1 argmax,
+ * so zs_greedy_step / zs_greedy_step_map (nblk = 1) do the stop / length / done bookkeeping.
+ * logprob[r] (optional) = log softmax(logits[r])[tok] at temperature 1, unfiltered (what
+ * zs_nll_finalize sums for a caption); kept[r] (optional, [R][2]) = (number of tokens kept, their
+ * share of softmax(z)).  One workgroup per row, the row read once into registers; no sort, no
+ * atomics: the same inputs give the same bits.  A row that is -inf everywhere is not meaningful
+ * (the last token is returned).
+ * Accepts: R > 0, 1 <= V <= 65536, ld >= V, temperature > 0, top_p > 0 (>= 1: off), top_k >= 0
+ * (0 or >= V: off), pointers 4-byte aligned (rows that all start on 16 bytes are read as float4);
+ * everything else is refused before a launch. */
+int zs_sample_rows(const float* logits, int R, int V, int ld, const int* row_id,
+                   const int* step_ctr, long seed, float temperature, int top_k, float top_p,
+                   float* part_val, int* part_idx, float* logprob, float* kept, void* stream);
+
 /* zs_gpt2_decode_persist: every remaining step of generate2 (gpt2_prefix_eval.py:161-222: the
  * 67-step loop of model.gpt(inputs_embeds=...) -> argmax -> stop check) for ONE batch of R <= 64
  * rows (the reference's eval batch), bf16, as one persistent launch of `grid` (48, 96 or 192)

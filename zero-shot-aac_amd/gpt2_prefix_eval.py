@@ -1,7 +1,9 @@
 """Drop-in for the reference's decoding entry points (gpt2_prefix_eval.py):
 
     generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_count=1,
-              entry_length=67, top_p=0.8, temperature=1., stop_token='.') -> str      (161-222)
+              entry_length=67, top_p=0.8, temperature=1., stop_token='.',
+              do_sample=False, seed=0) -> str                                          (161-222)
+    generate2_samples(... same, seed=0, top_k=0) -> list[str]   (all entry_count sampled texts)
     generate_beam(model, tokenizer, beam_size=5, prompt=None, embed=None, entry_length=67,
                   temperature=1., stop_token='.') -> list[str]                        (99-158)
     get_prefix_tokens(prefix_embed, embeddings, tokenizer) -> (str,)                  (271-278)
@@ -27,7 +29,7 @@ import torch.nn.functional as nnf
 from zsaac import ops
 from zsaac.modules import require_device
 
-__all__ = ["generate2", "generate_beam", "get_prefix_tokens", "generate_beam_magic", "magic_search",
+__all__ = ["generate2", "generate2_samples", "generate_beam", "get_prefix_tokens", "generate_beam_magic", "magic_search",
            "compute_audio_text_similarity_via_embeddings", "compute_audio_text_similarity_via_raw_text"]
 
 
@@ -53,11 +55,18 @@ def _temperature(temperature) -> float:
 
 
 def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_count=1, entry_length=67,
-              top_p=0.8, temperature=1., stop_token: str = '.'):
+              top_p=0.8, temperature=1., stop_token: str = '.', do_sample: bool = False, seed: int = 0):
     """Greedy: the top-p filter never removes the highest-probability token, so the pick is the
     argmax (gpt2_prefix_eval.py:194-212); stop after appending ``stop_token`` or 764 (' .').
     Like the reference, the returned text starts with the prompt tokens (``tokens`` or the
-    encoded ``prompt``) when no ``embed`` is given (lines 182-184, 209-210, 218)."""
+    encoded ``prompt``) when no ``embed`` is given (lines 182-184, 209-210, 218).
+    ``do_sample=True``: ``top_p``, ``temperature`` and ``entry_count`` act (zs_sample_rows draws
+    from the nucleus instead of taking its first token); the first of the ``entry_count`` texts
+    is returned, as the reference returns ``generated_list[0]`` (line 222).  All of them:
+    :func:`generate2_samples`."""
+    if do_sample:
+        return generate2_samples(model, tokenizer, tokens, prompt, embed, entry_count, entry_length,
+                                 top_p, temperature, stop_token, seed)[0]
     if embed is None:
         if tokens is None:
             tokens = torch.tensor(tokenizer.encode(prompt)).unsqueeze(0)
@@ -72,6 +81,31 @@ def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_coun
     ids, ln = dec.greedy(1, P)
     out = head + ids[0, :int(ln[0])].tolist()
     return tokenizer.decode(out)
+
+
+def generate2_samples(model, tokenizer, tokens=None, prompt=None, embed=None, entry_count=1,
+                      entry_length=67, top_p=0.8, temperature=1., stop_token: str = '.',
+                      seed: int = 0, top_k: int = 0) -> List[str]:
+    """generate2's ``entry_count`` loop (gpt2_prefix_eval.py:180-220) with a real draw: the
+    ``entry_count`` texts sampled from the top-p nucleus of softmax(logits / temperature), as one
+    batch of ``entry_count`` rows over one prefill.  Row j draws with Philox(seed, counter (j,
+    step)): the same arguments give the same texts."""
+    if embed is None:
+        if tokens is None:
+            tokens = torch.tensor(tokenizer.encode(prompt)).unsqueeze(0)
+        dev = next(model.parameters()).device
+        embed = model.gpt.transformer.wte(tokens.to(dev))
+    head = [] if tokens is None else [int(t) for t in torch.as_tensor(tokens).reshape(-1).tolist()]
+    n = int(entry_count)
+    if n < 1:
+        raise ValueError("entry_count must be at least 1")
+    dec, P = _decoder(model, embed, entry_length, n)
+    dec.prefill(1, P, row_stride=n)
+    dec.stop0 = tokenizer.encode(stop_token)[0]
+    ids, ln, _ = dec.sample(1, n, P, temperature=_temperature(temperature), top_p=top_p, top_k=top_k,
+                            seed=seed)
+    ids, ln = ids.cpu(), ln.cpu()
+    return [tokenizer.decode(head + ids[j, :int(ln[j])].tolist()) for j in range(n)]
 
 
 def generate_beam(model, tokenizer, beam_size: int = 5, prompt=None, embed=None, entry_length=67,

@@ -303,7 +303,7 @@ class _ZsMistralModel(nn.Module):
 
 class ZsMistralForCausalLM(nn.Module):
     """MistralForCausalLM's module tree / keys (``model.*``, ``lm_head``); ``generate`` with
-    inputs_embeds runs the HIP decoder (greedy only, as the reference calls it)."""
+    inputs_embeds runs the HIP decoder (greedy, as the reference calls it, or sampled)."""
 
     def __init__(self, config: dict):
         super().__init__()
@@ -341,12 +341,30 @@ class ZsMistralForCausalLM(nn.Module):
         return dec
 
     def generate(self, inputs_embeds=None, attention_mask=None, do_sample=False, max_length=60,
-                 eos_token_id=2, pad_token_id=2, **kw):
-        """Greedy generate over inputs_embeds with an all-ones mask (the only call the reference
-        makes, predict_mistralai_multilingual.py:105-111): [B, max_length - P] ids, rows that
-        finished padded with ``pad_token_id`` (HF's output)."""
-        if do_sample or kw.get("num_beams", 1) != 1:
-            raise NotImplementedError("only greedy generate (do_sample=False) is provided")
+                 eos_token_id=2, pad_token_id=2, top_k=50, top_p=1.0, temperature=1.0,
+                 num_return_sequences=1, seed=None, **kw):
+        """Generate over inputs_embeds with an all-ones mask (the only call the reference makes,
+        predict_mistralai_multilingual.py:105-111, is the greedy one): [B, max_length - P] ids,
+        rows that finished padded with ``pad_token_id`` (HF's output).  ``do_sample=True``:
+        ``temperature``, ``top_k`` (HF's default 50; 0 = off) and ``top_p`` filter in HF's order
+        and zs_sample_rows draws; ``num_return_sequences=n`` gives [B * n, width], sequence b's
+        samples in rows b*n .. b*n + n - 1.  ``seed=None`` takes the Philox key from torch's
+        default generator, so torch.manual_seed reproduces a run."""
+        if kw.get("num_beams", 1) != 1:
+            raise NotImplementedError("beam search is not provided (num_beams must be 1)")
+        n = int(num_return_sequences)
+        sample = None
+        if do_sample:
+            if not (temperature > 0 and top_p > 0 and top_k >= 0 and n >= 1):
+                raise ValueError("generate: temperature > 0, top_p > 0, top_k >= 0, "
+                                 "num_return_sequences >= 1")
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            sample = (float(temperature), int(top_k), float(top_p), int(seed))
+            if n > 1:
+                inputs_embeds = inputs_embeds.repeat_interleave(n, 0)
+        elif n != 1:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True")
         if attention_mask is not None and not bool((attention_mask == 1).all()):
             raise NotImplementedError("attention_mask must be all ones (as the reference passes)")
         require_device(inputs_embeds, "MistralForCausalLM.generate")
@@ -354,7 +372,8 @@ class ZsMistralForCausalLM(nn.Module):
         new = max(max_length - P, 0)
         # capacity by the call's upper bounds: any prompt up to 64 rows (or P), any new <= max_length
         dec = self.engine(inputs_embeds.device, max(B, 32), max(P, 64), max(max_length, 1))
-        rows = dec.generate_embeds(inputs_embeds, max_length=max_length, eos=eos_token_id)
+        rows = dec.generate_embeds(inputs_embeds, max_length=max_length, eos=eos_token_id,
+                                   sample=sample)
         # HF generate returns only as many columns as were generated: until every row emitted eos
         # (finished rows padded with pad_token_id) or max_length - P
         width = min(new, max([len(r) for r in rows] + [0]))

@@ -83,6 +83,7 @@ SIGNATURES = {
     "zs_prefix_ids_assemble": [P, I, P, P, I, I, I, P, P],
     "zs_greedy_step": [P, P, I, I, P, I, I, I, P, P, P, P, P, P, P],
     "zs_greedy_init": [I, P, P, P, P, P, I, P, P, P],
+    "zs_sample_rows": [P, I, I, I, P, P, L, F, I, F, P, P, P, P, P],
     "zs_decode_persist_workspace_bytes": [],
     "zs_gpt2_decode_persist": [I, I, I, I, I, I, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, L, I, I, P],
     "zs_gpt2_decode_phases": [I, I, I, I, I, I, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, L, I, I, P],

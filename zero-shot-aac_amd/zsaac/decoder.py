@@ -302,9 +302,10 @@ class Gpt2Decoder:
     def __init__(self, w: Gpt2Weights, max_rows: int, max_prompt: int, max_steps: int = 67,
                  max_prefill_rows: Optional[int] = None, topk: int = 8, chunk: int = 0,
                  use_graph: bool = True, compact: Optional[bool] = None,
-                 persist: Optional[bool] = None, alloc_kv: bool = True):
+                 persist: Optional[bool] = None, alloc_kv: bool = True, grid: bool = True):
         """alloc_kv False: no KV cache of its own -- share_rows gives it rows of another
-        decoder's (a group begin's sub-decoder)."""
+        decoder's (a group begin's sub-decoder).  grid False: a stepwise-only decoder (sampling):
+        no grid-decode workspace, no packed weights."""
         if chunk <= 0:   # a divisor of the steps after step 0, near 6 (no wasted tail steps)
             n = max(max_steps - 1, 1)
             cands = [c for c in range(4, 13) if n % c == 0]
@@ -369,7 +370,8 @@ class Gpt2Decoder:
         # f32 parity mode: the same grid decode in f32 (zs_gpt2_decode_persist_f32, G = 192)
         self.f32_grid = (dt == torch.float32 and self.R <= 64
                          and os.environ.get("ZSAAC_GRID_DECODE_F32", "1") != "0")
-        self.grid_decode = self.grid_decode or self.f32_grid
+        self.f32_grid = self.f32_grid and grid
+        self.grid_decode = (self.grid_decode and grid) or self.f32_grid
         if persist is None:
             persist = os.environ.get("ZSAAC_PERSIST", "1") != "0"
         self.persist = bool(persist) and self.grid_decode
@@ -722,6 +724,74 @@ class Gpt2Decoder:
         self.greedy_begin(B)
         self.run_to_completion()
         return self.out_ids[:B], self.out_len[:B]
+
+    # ---------------------------------------------------------------- sampling (generate2, do_sample)
+    def _sample_buffers(self, R, keep_logits):
+        b = getattr(self, "_smp", None)
+        if b is None or b["R"] < R:
+            dev, V = self.dev, self.w.V
+            Vp = -(-V // 4) * 4          # rows start on 16 bytes: zs_sample_rows reads float4
+            b = dict(R=R, logits=torch.empty(R, Vp, device=dev)[:, :V],
+                     pv=torch.empty(R, device=dev), pi=torch.empty(R, device=dev, dtype=torch.int32),
+                     lp=torch.empty(R, device=dev), lph=torch.empty(self.max_steps, R, device=dev),
+                     plen=torch.empty(R, device=dev, dtype=torch.int32),
+                     row_id=torch.empty(R, device=dev, dtype=torch.int32))
+            self._smp = b
+        hist = None
+        if keep_logits:
+            assert R * self.max_steps * self.w.V <= 1 << 28, "keep_logits is for tests (small V)"
+            hist = torch.zeros(self.max_steps, R, self.w.V, device=self.dev)
+        return b, hist
+
+    def sample(self, C: int, n: int, Pmax: int, temperature: float = 1.0, top_k: int = 0,
+               top_p: float = 1.0, seed: int = 0, clip_offset: int = 0, keep_logits: bool = False):
+        """After :meth:`prefill` (C rows, row_stride=n): n sampled continuations per clip
+        (generate2 with its ``top_p`` / ``temperature`` acting, gpt2_prefix_eval.py:194-212), on
+        rows c*n + j.  Stepwise: layers, ln_f, the LM-head GEMM to f32 logits, zs_sample_rows,
+        zs_greedy_step (nblk = 1).  Row c*n + j draws with the id (clip_offset + c)*n + j, so a
+        clip's samples depend on (seed, its index), not on its batch.  The n rows of a clip read
+        the prompt's K/V from row c*n through the kv-row table and write their own tokens' K/V
+        to their own rows.
+        Returns (ids [R, max_steps] int32, lengths [R] int32, logprob [R, max_steps] f32: log
+        softmax at temperature 1 of each emitted token, 0 past a row's length) and, with
+        ``keep_logits``, the logits of every step [max_steps, R, V] (zeros for steps not run)."""
+        R = C * n
+        assert 0 < R <= self.R and C <= self.Rp
+        temperature = float(temperature) if temperature > 0 else 1.0     # the reference's divisor
+        b, hist = self._sample_buffers(R, keep_logits)
+        dev = self.dev
+        rows = torch.arange(R, device=dev, dtype=torch.int32)
+        src = torch.div(rows, n, rounding_mode="floor") * n
+        b["plen"][:R].copy_(self.plen[:C].repeat_interleave(n))
+        b["row_id"][:R].copy_(rows + clip_offset * n)
+        plen, row_id, logits = b["plen"][:R], b["row_id"][:R], b["logits"][:R]
+        j = torch.arange(self.Lmax, device=dev, dtype=torch.int32)[None, :]
+        self.kvrow[:R].copy_(torch.where(j < plen[:, None], src[:, None], rows[:, None]))
+        if n > 1:
+            self.hf[:R].copy_(self.hf[:C].repeat_interleave(n, 0))
+        self._eager, self._persist_R, self._cgreedy = True, 0, None
+        ops.greedy_init(R, plen, self.pos, self.done, self.out_len, self.out_ids, self.max_steps,
+                        self.step_ctr, self.all_done)
+        b["lph"].zero_()
+        for t in range(self.max_steps):
+            if t:
+                self._decode_forward(R, kvrow=self.kvrow[:R])
+            ops.gemm(self.hf[:R], self.w.wte, logits, split_k=1)
+            if hist is not None:
+                hist[t].copy_(logits)
+            ops.sample_rows(logits, self.step_ctr, seed, b["pv"], b["pi"], temperature=temperature,
+                            top_k=top_k, top_p=top_p, row_id=row_id, logprob=b["lp"])
+            b["lph"][t, :R].copy_(b["lp"][:R])
+            ops.greedy_step(b["pv"], b["pi"], R, 1, self.step_ctr, self.max_steps, self.stop0,
+                            self.stop1, self.out_ids, self.out_len, self.done, self.pos,
+                            self.next_tok, self.all_done)
+            self.rows_stepped += R
+            if t % 8 == 7 and int(self.all_done[0].item()):
+                break
+        ids, ln = self.out_ids[:R].clone(), self.out_len[:R].clone()   # (the state is reused)
+        steps = torch.arange(self.max_steps, device=dev)[None, :]
+        lp = torch.where(steps < ln[:, None], b["lph"][:, :R].t(), torch.zeros((), device=dev))
+        return (ids, ln, lp) if hist is None else (ids, ln, lp, hist)
 
     # ---------------------------------------------------------------- beam (generate_beam)
     def _beam_step_body(self, C, beam):

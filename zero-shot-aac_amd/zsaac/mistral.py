@@ -450,8 +450,31 @@ class MistralDecoder:
     def _lm_argmax(self, a, B):
         ops.lmhead_topk(a, self.w.lm, 1, None, self.pval, self.pidx, M=B)
 
+    def _pick_step(self, a, B, eos, sample=None):
+        """The LM head over rows ``a`` and the step kernel.  ``sample`` None: the argmax partials
+        of zs_lmhead_topk.  ``sample`` = (temperature, top_k, top_p, seed): f32 logits by the
+        GEMM, then zs_sample_rows, whose (value, id) per row is an nblk = 1 partial; row b draws
+        with Philox(seed, counter (b, step))."""
+        pv, pi, nblk = self.pval, self.pidx, self.nblk
+        if sample is None:
+            self._lm_argmax(a, B)
+        else:
+            t, k, p, seed = sample
+            if getattr(self, "_slogits", None) is None:
+                V, dev = self.w.V, self.w.dev
+                self._slogits = torch.empty(self.B, -(-V // 4) * 4, device=dev)[:, :V]
+                self._spv = torch.empty(self.B, device=dev)
+                self._spi = torch.empty(self.B, device=dev, dtype=torch.int32)
+            pv, pi, nblk = self._spv, self._spi, 1
+            ops.gemm(a, self.w.lm, self._slogits[:B], split_k=1, M=B)
+            ops.sample_rows(self._slogits[:B], self.step_ctr, seed, pv, pi, temperature=t, top_k=k,
+                            top_p=p)
+        # max_steps = the row stride of out_ids (generate's loop stops after `new` steps)
+        ops.greedy_step(pv, pi, B, nblk, self.step_ctr, self.max_new, eos, eos, self.out_ids,
+                        self.out_len, self.done, self.pos, self.next_tok, self.all_done)
+
     def generate(self, hard_ids: torch.Tensor, soft: torch.Tensor, tail_ids: torch.Tensor,
-                 max_length: int = 60, eos: int = 2) -> List[List[int]]:
+                 max_length: int = 60, eos: int = 2, sample=None) -> List[List[int]]:
         """hard_ids [B, H] int32 (padded with 0 like padding_captions), soft [B, ns, D] f32 (the
         mapper rows), tail_ids [nt] int32 (the language tag's token ids) -> per sequence the
         generated ids up to and including eos (HF generate with inputs_embeds: at most
@@ -471,17 +494,14 @@ class MistralDecoder:
         self.pos[:M].copy_(torch.arange(P, device=w.dev, dtype=torch.int32).repeat(B))
         self._layers(M, P)
         self.last[:B].copy_(self.h[:M].view(B, P, w.D)[:, P - 1])
-        self._lm_argmax(self.last[:B], B)
         for t in (self.done, self.out_len, self.step_ctr, self.all_done, self.out_ids):
             t.zero_()
         self.pos[:B].fill_(P - 1)
-        # max_steps = the row stride of out_ids (the loop below stops after `new` steps)
-        ops.greedy_step(self.pval, self.pidx, B, self.nblk, self.step_ctr, self.max_new, eos, eos,
-                        self.out_ids, self.out_len, self.done, self.pos, self.next_tok, self.all_done)
+        self._pick_step(self.last[:B], B, eos, sample)
         for s in range(1, new):
             if s % 8 == 0 and int(self.all_done[0]):
                 break
-            self.decode_step(B, eos)
+            self.decode_step(B, eos, sample)
         ids, ln = self.out_ids[:B].cpu(), self.out_len[:B].cpu()
         return [ids[b, :int(ln[b])].tolist() for b in range(B)]
 
@@ -539,23 +559,20 @@ class MistralDecoder:
         ids, ln = self.out_ids[:B].cpu(), self.out_len[:B].cpu()
         return [ids[b, :int(ln[b])].tolist() for b in range(B)]
 
-    def _step_body(self, B, eos):
+    def _step_body(self, B, eos, sample=None):
         w, st = self.w, torch.cuda.current_stream().cuda_stream
         call("zs_mistral_embed", None, 0, None, 0, None, 0, self.next_tok.data_ptr(),
              w.emb.data_ptr(), w.D, B, self.x.data_ptr(), ops.dt(w.emb), st)
         self._layers(B, 1)
-        self._lm_argmax(self.h[:B], B)
-        ops.greedy_step(self.pval, self.pidx, B, self.nblk, self.step_ctr, self.max_new, eos, eos,
-                        self.out_ids, self.out_len, self.done, self.pos, self.next_tok,
-                        self.all_done)
+        self._pick_step(self.h[:B], B, eos, sample)
 
-    def decode_step(self, B: int, eos: int = 2):
+    def decode_step(self, B: int, eos: int = 2, sample=None):
         """One greedy step of B sequences (every operand on the device: token ids, positions, KV
         caches, stop flags), replayed from a hipGraph captured on first use per (B, eos): the
         ~290 launches of a 32-layer step are one graph launch instead of ~290 host round trips
         through the C-ABI."""
-        if not self.use_graph:
-            return self._step_body(B, eos)
+        if not self.use_graph or sample is not None:    # a sampled step runs launch by launch
+            return self._step_body(B, eos, sample)
         key = (B, eos, self.fused_decode_attn, self.fused_glu, tuple(sorted(self.run_cfg.items())))
         g = self.graphs.get(key)
         if g is None:
@@ -582,7 +599,7 @@ class MistralDecoder:
         return self.h[:M].float().view(B, P, w.D).clone()
 
     def generate_embeds(self, embeds: torch.Tensor, max_length: int = 60,
-                        eos: int = 2) -> List[List[int]]:
+                        eos: int = 2, sample=None) -> List[List[int]]:
         """HF ``generate(inputs_embeds=embeds, attention_mask=ones, do_sample=False, ...)`` from
         already assembled prompt rows [B, P, D] (the drop-in's entry point)."""
         B = embeds.shape[0]
@@ -590,7 +607,7 @@ class MistralDecoder:
         empty = torch.zeros(B, 0, dtype=torch.int32, device=dev)
         return self.generate(empty, embeds.float().contiguous(), torch.zeros(0, dtype=torch.int32,
                                                                               device=dev),
-                             max_length=max_length, eos=eos)
+                             max_length=max_length, eos=eos, sample=sample)
 
 
 def generate_concurrent(decoders: Sequence["MistralDecoder"], streams: Sequence, jobs):

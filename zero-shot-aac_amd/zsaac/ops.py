@@ -593,6 +593,31 @@ def greedy_step_map(part_val, part_idx, R, rowmap, nphys, nblk, step_ctr, max_st
          _p(next_tok), _p(all_done), _s())
 
 
+def sample_rows(logits, step_ctr, seed, part_val, part_idx, temperature=1.0, top_k=0, top_p=1.0,
+                row_id=None, logprob=None, kept=None, R=None):
+    """zs_sample_rows: one token per row of ``logits`` [R, V] f32 (rows of stride
+    logits.stride(0)) by temperature -> top-k -> top-p -> Philox draw keyed by (seed, row_id,
+    *step_ctr); part_val / part_idx [R] are nblk = 1 argmax partials for greedy_step."""
+    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1,
+          "sample_rows: logits are [R, V] f32 with unit column stride")
+    R = R if R is not None else logits.shape[0]
+    _need(0 < R <= logits.shape[0], "sample_rows: R")
+    _i32(step_ctr, "step_ctr"), _i32(row_id, "row_id"), _i32(part_idx, "part_idx")
+    _need(part_val.dtype == torch.float32 and part_val.is_contiguous() and part_idx.is_contiguous()
+          and part_val.numel() >= R and part_idx.numel() >= R, "sample_rows: part_val / part_idx [R]")
+    _need(row_id is None or (row_id.is_contiguous() and row_id.numel() >= R), "sample_rows: row_id [R]")
+    _need(logprob is None or (logprob.dtype == torch.float32 and logprob.is_contiguous()
+                              and logprob.numel() >= R), "sample_rows: logprob is [R] f32")
+    _need(kept is None or (kept.dtype == torch.float32 and kept.is_contiguous()
+                           and kept.numel() >= 2 * R), "sample_rows: kept is [R, 2] f32")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if seed >= 1 << 63:
+        seed -= 1 << 64
+    call("zs_sample_rows", _p(logits), R, logits.shape[1], logits.stride(0), _p(row_id),
+         _p(step_ctr), seed, float(temperature), int(top_k), float(top_p), _p(part_val),
+         _p(part_idx), _p(logprob), _p(kept), _s())
+
+
 def beam_step(part_stat, part_val, part_idx, C, beam, nblk, topk, first, stop, step_ctr,
               max_steps, scores, seq_len, stopped, tokens, tokens_tmp, kvrow, kvrow_tmp, Lmax,
               pos, next_tok, all_done):

@@ -16,7 +16,7 @@ import dataclasses
 import os
 import time
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -81,6 +81,36 @@ class CaptionBatch:
     def prefix_token_lists(self) -> List[List[int]]:
         pid, pl = self.prefix_ids.cpu().numpy(), self.plen.cpu().numpy()
         return [pid[b, :pl[b]].tolist() for b in range(pid.shape[0])]
+
+
+@dataclass
+class SampleBatch:
+    """CaptionPipeline.sample_emb's result: n sampled captions per clip."""
+    ids: torch.Tensor          # [B, n, steps] int32
+    lengths: torch.Tensor      # [B, n] int32
+    logprobs: torch.Tensor     # [B, n, steps] f32: log softmax (temperature 1) of each token, 0 past the end
+    hard_ids: torch.Tensor     # [B, h_cap] int32 (0-padded)
+    hard_len: torch.Tensor     # [B]
+    plen: torch.Tensor         # [B]
+    clap_emb: torch.Tensor     # [B, 1024]
+    prefix_ids: Optional[torch.Tensor] = None   # [B, Pmax] int32 get_prefix_tokens ids
+    logits: Optional[torch.Tensor] = None    # keep_logits: [steps, B * n, V]
+
+    def samples(self) -> List[List[List[int]]]:
+        ids, ln = self.ids.cpu().numpy(), self.lengths.cpu().numpy()
+        return [[ids[b, j, :ln[b, j]].tolist() for j in range(ids.shape[1])]
+                for b in range(ids.shape[0])]
+
+    def prefix_token_lists(self) -> List[List[int]]:
+        pid, pl = self.prefix_ids.cpu().numpy(), self.plen.cpu().numpy()
+        return [pid[b, :pl[b]].tolist() for b in range(pid.shape[0])]
+
+    def sum_logprob(self) -> torch.Tensor:
+        """[B, n]: log p(caption | clip), what CaptionScorer reports for the same ids."""
+        return self.logprobs.sum(-1)
+
+    def mean_logprob(self) -> torch.Tensor:
+        return self.sum_logprob() / self.lengths.clamp(min=1)
 
 
 # token ids prompt_kernel (csrc/gpt2.hip) writes around the labels: "There", " are",
@@ -218,6 +248,7 @@ class CaptionPipeline:
         self.embed = torch.empty(B * self.Pmax, 768, device=dev)
         self.prefix_ids = torch.zeros(B * self.Pmax, **i32)
         self.emb_buf = torch.empty(B, 1024, device=dev)
+        self._sample_decs: Dict[int, Gpt2Decoder] = {}    # sample_decoder's, by samples per clip
 
     def _setup_tables(self, label_table, label_tokens):
         cfg, dev = self.cfg, self.dev
@@ -260,6 +291,7 @@ class CaptionPipeline:
     def result(self) -> CaptionBatch:
         """Views of the current batch's outputs (valid until the next begin_*)."""
         B, cfg, dec = self._B, self.cfg, self.decoder
+        assert B is not None, "result(): no begin_emb since the last sample_emb"
         if cfg.beam:
             R = B * cfg.beam
             ids = dec.out_ids[:R].view(B, cfg.beam, -1)
@@ -286,6 +318,20 @@ class CaptionPipeline:
         batch of CLAP embeddings, without any host synchronisation."""
         cfg, B, Pmax = self.cfg, emb.shape[0], self.Pmax
         self._B, self._emb = B, emb
+        dec = self.decoder
+        self._prompt_stage(emb, dec)
+        if cfg.beam:
+            dec.prefill(B, Pmax, row_stride=cfg.beam)
+            dec.beam_begin(B, cfg.beam)
+        else:
+            dec.prefill(B, Pmax)
+            dec.greedy_begin(B)
+
+    def _prompt_stage(self, emb: torch.Tensor, dec: Gpt2Decoder):
+        """Prompt assembly, mapper, the prompt rows into ``dec.x`` (with dec.plen /
+        dec.last_row) and get_prefix_tokens: the begin up to the prefill, for the decoder that
+        will run it."""
+        cfg, B, Pmax = self.cfg, emb.shape[0], self.Pmax
         assert B <= cfg.batch
         ops.prompt_assemble(emb, self.labels, cfg.sound_effect_num, self.label_tok, self.label_len,
                             self.hard_ids[:B], self.hard_len[:B])
@@ -295,18 +341,45 @@ class CaptionPipeline:
         else:
             prefix.copy_(emb)
         soft = self.mapper(prefix)
-        dec = self.decoder
         ops.prefill_embed(self.hard_ids[:B], self.hard_len[:B], soft, self.mapper.soft_ld,
                           cfg.prefix_length, self.gpt.wte, self.gpt.wpe, B, Pmax,
                           self.embed[:B * Pmax], dec.x, dec.plen, dec.last_row)
         if cfg.prefix_tokens:
             self.prefix_tokens(B, soft)
-        if cfg.beam:
-            dec.prefill(B, Pmax, row_stride=cfg.beam)
-            dec.beam_begin(B, cfg.beam)
-        else:
-            dec.prefill(B, Pmax)
-            dec.greedy_begin(B)
+
+    # ------------------------------------------------------------------ sampling
+    def sample_decoder(self, n: int) -> Gpt2Decoder:
+        """The stepwise decoder of batch * n rows that sample_emb runs on (built on first use;
+        the greedy / beam decoder, its graphs and the persistent grid are not involved)."""
+        decs = self._sample_decs
+        if n not in decs:
+            cfg = self.cfg
+            decs[n] = Gpt2Decoder(self.gpt, cfg.batch * n, self.Pmax, cfg.entry_length,
+                                  max_prefill_rows=cfg.batch, use_graph=False, compact=False,
+                                  persist=False, grid=False)
+        return decs[n]
+
+    def sample_emb(self, emb: torch.Tensor, n: int, temperature: float = 1.0, top_k: int = 0,
+                   top_p: float = 1.0, seed: int = 0, clip_offset: int = 0,
+                   keep_logits: bool = False) -> "SampleBatch":
+        """n sampled captions per clip from CLAP audio embeddings [B, 1024]: the greedy begin
+        (prompt, mapper, prefill), then Gpt2Decoder.sample, on the current stream.  Clip b draws
+        with the ids (clip_offset + b) * n + j: give each batch of a dataset its first clip's
+        index and a clip's captions do not depend on the batching."""
+        cfg, B, Pmax, dec = self.cfg, emb.shape[0], self.Pmax, self.sample_decoder(n)
+        # the prompt stage rewrites the buffers a pending begin_emb's result() views (hard_ids,
+        # prefix_ids): that batch is over
+        self._B = self._emb = None
+        self._prompt_stage(emb, dec)
+        dec.prefill(B, Pmax, row_stride=n)
+        out = dec.sample(B, n, self.Pmax, temperature, top_k, top_p, seed, clip_offset, keep_logits)
+        ids, ln, lp = out[:3]
+        pid = self.prefix_ids[:B * Pmax].view(B, Pmax) if cfg.prefix_tokens else None
+        return SampleBatch(ids.view(B, n, -1), ln.view(B, n), lp.reshape(B, n, -1), self.hard_ids[:B],
+                           self.hard_len[:B], dec.plen[:B], emb, pid, out[3] if keep_logits else None)
+
+    def sample_wav(self, wav: torch.Tensor, n: int, **kw) -> "SampleBatch":
+        return self.sample_emb(self.encode(wav), n, **kw)
 
 
 def persist_grids(env: Optional[str] = None) -> List[int]:

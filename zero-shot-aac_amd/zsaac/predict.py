@@ -25,6 +25,9 @@ text tower and ``--bert_vocab`` its WordPiece vocabulary (bert-base-uncased's vo
 ``--memory PKL [PKL ...]`` projects every audio embedding onto the text memory bank built from
 those pickles before captioning (``map2memory`` / ``construct_support_memory``,
 predict_prompt.py:23-56; zsaac.memory), with softmax scale ``--memory_scale`` (default 100).
+``--sample N`` draws N captions per clip from generate2's nucleus (``--top_p``, ``--top_k``,
+``--temperature``, ``--seed``; zs_sample_rows) into ``samples.json`` and writes the one with the
+highest mean log-probability per token to ``output.txt``; it combines with ``--memory`` only.
 """
 from __future__ import annotations
 
@@ -157,6 +160,44 @@ def make_preds(pipe: CaptionPipeline, tokenizer, all_data: List[Dict], memory=No
             key2pred[it["audio_id"]] = [tokenizer.decode(ids).lower()]
             key2pred_prefix[it["audio_id"]] = [tokenizer.decode(pids)]
     return key2pred, key2pred_prefix, key2refs
+
+
+def make_preds_sample(pipe: CaptionPipeline, tokenizer, all_data: List[Dict], n: int,
+                      temperature: float = 1.0, top_k: int = 0, top_p: float = 0.8, seed: int = 0,
+                      memory=None, memory_scale: float = 100.0):
+    """``--sample N``: N sampled captions per clip (CaptionPipeline.sample_emb; clip i of the
+    pickle draws with the ids i * N + j whatever the batch size).  Returns make_preds' three
+    dicts, key2pred holding the sample with the highest mean log-probability per token, and
+    {audio_id: [{"caption", "sum_logprob", "mean_logprob", "tokens"}] * N}."""
+    key2refs = {it["audio_id"]: post_processing(it.get("caption", [])) for it in all_data}
+    key2pred: Dict[str, List[str]] = {}
+    key2pred_prefix: Dict[str, List[str]] = {}
+    key2samples: Dict[str, List[Dict]] = {}
+    B = pipe.cfg.batch
+    for c0 in range(0, len(all_data), B):
+        chunk = all_data[c0:c0 + B]
+        emb = safeload.stack_rows([it["audio_embedding"] for it in chunk]).to(pipe.dev)
+        if memory is not None:
+            emb = memory.project(emb, scale=memory_scale)
+        out = pipe.sample_emb(emb, n, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                              clip_offset=c0)
+        sums, means = out.sum_logprob().tolist(), out.mean_logprob().tolist()
+        for b, (it, caps, pids) in enumerate(zip(chunk, out.samples(), out.prefix_token_lists())):
+            rows = [{"caption": tokenizer.decode(ids).lower(), "sum_logprob": sums[b][j],
+                     "mean_logprob": means[b][j], "tokens": len(ids)} for j, ids in enumerate(caps)]
+            best = max(range(n), key=lambda j: (means[b][j], -j))
+            key2samples[it["audio_id"]] = rows
+            key2pred[it["audio_id"]] = [rows[best]["caption"]]
+            key2pred_prefix[it["audio_id"]] = [tokenizer.decode(pids)]
+    return key2pred, key2pred_prefix, key2refs, key2samples
+
+
+def write_samples(test_dir: str, key2samples) -> None:
+    """samples.json: {"samples": [{"filename", "captions": [{caption, sum_logprob, mean_logprob,
+    tokens}]}]}."""
+    with open(os.path.join(test_dir, "samples.json"), "w") as f:
+        json.dump({"samples": [{"filename": k, "captions": v} for k, v in key2samples.items()]},
+                  f, indent=4)
 
 
 def make_preds_magic(pipe: CaptionPipeline, tokenizer, all_data: List[Dict], clap_sd, bert_tok,
@@ -297,9 +338,20 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          "bank before captioning (map2memory, predict_prompt.py:23-56)")
     ap.add_argument("--memory_scale", type=float, default=100.0,
                     help="--memory: the softmax scale (the reference's 100)")
+    ap.add_argument("--sample", type=int, default=0, metavar="N",
+                    help="N sampled captions per clip (samples.json); output.txt gets the one with "
+                         "the highest mean log-probability")
+    ap.add_argument("--top_p", type=float, default=0.8, help="--sample: nucleus mass (generate2's 0.8)")
+    ap.add_argument("--top_k", type=int, default=0, help="--sample: keep the k largest logits (0: off)")
+    ap.add_argument("--temperature", type=float, default=1.0, help="--sample: logits divisor")
+    ap.add_argument("--seed", type=int, default=0, help="--sample: Philox key")
     args = ap.parse_args(argv)
     if args.memory and (args.magic or args.score):
         ap.error("--memory cannot be combined with --magic or --score")
+    if args.sample and (args.isbeam or args.magic or args.score):
+        ap.error("--sample cannot be combined with --isbeam, --magic or --score")
+    if args.sample < 0 or (args.sample and (args.top_p <= 0 or args.top_k < 0)):
+        ap.error("--sample needs N >= 1, --top_p > 0 and --top_k >= 0")
     if args.magic and not (args.clap and args.bert_vocab):
         raise SystemExit("--magic needs --clap <checkpoint> and --bert_vocab <vocab.txt>")
     params = load_params(args.test_dir)
@@ -330,8 +382,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if args.memory:
             from .memory import SupportMemory, construct_support_memory
             memory = SupportMemory(construct_support_memory(args.memory), dtype=dtype, device=pipe.dev)
-        key2pred, key2pred_prefix, key2refs = make_preds(pipe, tokenizer, all_data, memory,
-                                                         args.memory_scale)
+        if args.sample:
+            key2pred, key2pred_prefix, key2refs, key2samples = make_preds_sample(
+                pipe, tokenizer, all_data, args.sample, args.temperature, args.top_k, args.top_p,
+                args.seed, memory, args.memory_scale)
+            write_samples(args.test_dir, key2samples)
+        else:
+            key2pred, key2pred_prefix, key2refs = make_preds(pipe, tokenizer, all_data, memory,
+                                                             args.memory_scale)
     write_outputs(args.test_dir, key2pred, key2pred_prefix, key2refs)
     return 0
 
