@@ -1,6 +1,6 @@
-"""Plain CPU references of the GEMM family (csrc/gemm.hip, gemm_fast.h, gemm_core.h, gemm_rows.hip,
-gemm_skinny.hip): zs_gemm, zs_gemm_ln, zs_gemm_ln_f32 and zs_lmhead_topk(_t), one function per
-entry point, and the strided cases the GPU tests run.
+"""Plain CPU references of the GEMM family (csrc/gemm.hip, lmhead.hip, gemm_fast.h, gemm_core.h,
+gemm_rows.hip, gemm_skinny.hip): zs_gemm, zs_gemm_ln, zs_gemm_ln_f32 and zs_lmhead_topk(_t), one
+function per entry point, and the strided cases the GPU tests run.
 
 Pure torch on the CPU; every float is computed in ``dtype``: float64 is the reference, float32
 the yardstick (the same formula in the kernels' accumulation precision; its distance from the
@@ -30,7 +30,7 @@ from mistral_ref import tolerance  # noqa: F401  (the one rule, re-exported)
 F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
 NAN = float("nan")
 INF = float("inf")
-LM_BN = 128                  # gemm.hip LM_BN: vocabulary columns per partial block
+LM_BN = 128                  # lmhead.hip LM_BN: vocabulary columns per partial block
 PAD_IDX = 0x7fffffff         # index of a padding entry of a short block (value -inf)
 ACTS = ("none", "gelu_erf", "gelu_tanh", "relu", "tanh")     # = ACT_NONE .. ACT_TANH (0 .. 4)
 
@@ -179,8 +179,8 @@ def lmhead(a, w, topk, row_norm=False, temperature=1.0, dtype=F64, mut=""):
 
 
 def bubble_insert(vals, k, fixed):
-    """CPU emulation of lmhead_kernel's select-only register insertion for one lane: ``vals`` in
-    increasing index order.  fixed=False is the loop before the tie-order fix (a bubble whose
+    """CPU emulation of topk_insert (csrc/lmhead.hip), the select-only register insertion of one
+    lane: ``vals`` in increasing index order.  fixed=False is the loop before the tie-order fix (a bubble whose
     displaced entry is compared with strict > against its successor); True is the kernel's loop:
     lt[q] = cv > tv[q] on the old list, slot q takes cv where lt[q] and not lt[q - 1] and its upper
     neighbour where both hold.  -> [(value, index)] of length k."""
@@ -484,10 +484,11 @@ def lm_stat_tolerance(r64, r32):
 
 
 def lane_subsets(path, V, BM=64):
-    """The column subsets of block 0 that one lane (one thread) of lmhead_kernel scans in index
-    order before any merge: "ring" = the transposed register epilogue (32 columns per lane: 4-wide
-    groups 8 apart in each 32-column MFMA tile, two tiles per wave row), "tile" = the LDS tile
-    epilogue (128 / (256 / BM) consecutive columns per thread)."""
+    """The column subsets of block 0 that one lane (one thread) of the LM head scans in index
+    order before any merge: "ring" = lmhead_kernel's transposed register epilogue (for_token_cols
+    of csrc/lmhead.hip: 32 columns per lane, 4-wide groups 8 apart in each 32-column MFMA tile, two
+    tiles per wave row), "tile" = lmhead_tile_kernel's LDS tile epilogue (128 / (256 / BM)
+    consecutive columns per thread)."""
     subs = []
     if path == "ring":
         for wr0 in (0, 64):

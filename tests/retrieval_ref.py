@@ -1,4 +1,4 @@
-"""Plain CPU references of the retrieval kernels (zs_sim_rank of csrc/gemm.hip,
+"""Plain CPU references of the retrieval kernels (zs_sim_rank of csrc/lmhead.hip,
 zs_sim_topk_finalize of csrc/gpt2.hip) and of zsaac/retrieval.py, written from their definitions,
 and the cases the GPU tests run.
 

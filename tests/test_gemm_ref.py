@@ -253,7 +253,7 @@ def test_knob_defaults_match_the_library():
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                         "zero-shot-aac_amd", "csrc")
-    text = "".join(open(os.path.join(csrc, f)).read() for f in ("gemm.hip", "gemm_rows.hip", "gemm_skinny.hip"))
+    text = "".join(open(os.path.join(csrc, f)).read() for f in ("gemm.hip", "lmhead.hip", "gemm_rows.hip", "gemm_skinny.hip"))
     for k, v in R.KNOB_DEFAULTS.items():
         m = re.search(r"^(?:static )?int g_%s = (\w+);" % k, text, re.M)
         assert m, k

@@ -1,4 +1,4 @@
-"""zs_sim_rank (csrc/gemm.hip) and zs_sim_topk_finalize (csrc/gpt2.hip) against
+"""zs_sim_rank (csrc/lmhead.hip) and zs_sim_topk_finalize (csrc/gpt2.hip) against
 tests/retrieval_ref.py.  Operands are NaN-padded views of [rows + 1][ld] buffers (a padding column
 or the extra row read shows as NaN), outputs are sentinel-filled with a guard row behind them.
 

@@ -119,6 +119,37 @@ def test_lmhead_nll_rows_permute_and_repeat(cuda, dt):
         assert torch.equal(moved[k], one[k][perm]), k
 
 
+@pytest.mark.parametrize("xcd", [0, 1])
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("K", [128, 96])             # lean_mainloop; fast_mainloop (K % 64 != 0)
+@pytest.mark.parametrize("M", [130, 40])             # the 128-row tile twice (one ragged); the 64-row
+def test_lmhead_nll_partials_equal_lmhead_topk(cuda, M, K, dt, xcd):
+    """Bitwise: zs_lmhead_nll's per-block statistics and top-1 are the ones zs_lmhead_topk
+    (topk 1, part_stat given, no row_norm) writes on the same inputs -- what scoring relies on to
+    agree with the beam's log-probs.  V = 1000: 8 blocks, the last one partial; both block orders."""
+    from zsaac._lib import call
+    from gemm_ref import KNOB_DEFAULTS
+    ops = _ops()
+    V = 1000
+    d = R.lm_case(V, M, K, dt)
+    a, w = d["a"].to(cuda), d["w"].to(cuda)
+    nblk = ops.lmhead_nblk(V)
+    assert nblk == 8
+    call("zs_tune_set", b"fast_xcd", xcd)
+    try:
+        ps, pv, pi = (Out(cuda, (M, nblk, 2), torch.float32, SENT),
+                      Out(cuda, (M, nblk, 1), torch.float32, SENT), Out(cuda, (M, nblk, 1), I32, -7))
+        ops.lmhead_topk(a, w, 1, ps.t, pv.t, pi.t)
+        torch.cuda.synchronize()
+        got = _run_nll(cuda, a, w, d["tgt"], 1, M)
+    finally:
+        call("zs_tune_set", b"fast_xcd", KNOB_DEFAULTS["fast_xcd"])
+    assert bool((ps.cpu() != SENT).all()) and bool((got["ps"] != SENT).all())
+    assert torch.equal(got["ps"], ps.cpu())
+    assert torch.equal(got["pv"], pv.cpu()[..., 0])
+    assert torch.equal(got["pi"], pi.cpu()[..., 0])
+
+
 @pytest.mark.parametrize("Tmax", [1, 67, 130])
 def test_nll_finalize_caption_reduction(cuda, Tmax):
     """zs_nll_finalize alone on hand-made partials (one block, max 0, sum-exp 1: lse = 0, so

@@ -1,6 +1,5 @@
-// MFMA GEMM for every Linear/Conv1D on the hot path, plus the LM-head GEMM with a fused
-// per-row max / sum-exp / top-k epilogue (greedy argmax, beam log-softmax top-k,
-// get_prefix_tokens cosine argmax).
+// MFMA GEMM for every Linear/Conv1D on the hot path (the LM head and its kin, which reduce their
+// output blocks in registers instead of storing them, are in lmhead.hip).
 //
 //   out[m][n] = act(sum_k A[m][k] * W[n][k] + bias[n]) + residual[m][n]
 //
@@ -824,630 +823,6 @@ static int dispatch_gemm(GemmArgs& g, hipStream_t st) {
   return launch_gemm<T, 128, 64>(g, st);
 }
 
-// ------------------------------------------------------------------ LM head (+ row reductions)
-constexpr int LM_BN = 128;
-constexpr int MAXK = 8;
-int g_lm_prio = 1;   // zs_tune_set("lm_prio", 0): LM head main loop without s_setprio
-
-// RING (f32 only; bf16 always): the LDS-DMA ring main loop and the transposed register epilogue
-// (f32 rows staged as bf16 rows of twice the length, fast_compute F32)
-template <typename T, int BM, int KMAX, bool RING = sizeof(T) == 2>
-__global__ __launch_bounds__(256) void lmhead_kernel(int xcd_order, int M, int K, int V, const T* A, int lda,
-                                                     const T* W, int topk, int row_norm,
-                                                     float* part_stat, float* part_val,
-                                                     int* part_idx, float temp) {
-  // temp != 1: logits / temp before the top-k and the softmax statistics (generate2 /
-  // generate_beam's `temperature`, gpt2_prefix_eval.py:121, 196); a true division, as the reference
-  const bool tdiv = temp != 1.0f;
-  constexpr int LDW = BK + GemmTraits<T>::PAD;
-  constexpr int TM = BM / 64, TN = LM_BN / 64;
-  constexpr int SM_MAIN = 2 * (BM + LM_BN) * LDW * (int)sizeof(T);
-  constexpr int SM_EPI = BM * (LM_BN + 1) * 4;
-  constexpr bool FAST = RING;
-  constexpr int SM_LOOP = FAST ? 2 * FastTile<BM, LM_BN>::STAGE : SM_MAIN;  // 4 waves (2x2)
-  constexpr int SM = SM_LOOP > SM_EPI ? SM_LOOP : SM_EPI;
-  // ONE __shared__ array (a second object can de-pipeline the DMA loop: §5 item 4(a))
-  __shared__ __attribute__((aligned(16))) char smem_raw[SM + BM * 4];
-  float* inv_norm = reinterpret_cast<float*>(smem_raw + SM);
-  // 1-D grid of nblk x ntm blocks.  XCD-local order: workgroup b runs on XCD b % 8; the remap
-  // gives each XCD a contiguous range of u, and u walks the row tiles fastest, so every row tile
-  // of a vocab block runs on the same XCD at about the same time: each 128-token W slice is
-  // fetched into one L2 once and reused by all row tiles (with the vocab block fastest, the
-  // 77 MB of W streamed once per row tile).
-  const int ntm = cdiv(M, BM), nblk = cdiv(V, LM_BN), nwg = nblk * ntm;
-  int vb, mb;
-  if (xcd_order & 1) {
-    const int b = blockIdx.x, x = b & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (b >> 3);
-    vb = u / ntm;
-    mb = u - vb * ntm;
-  } else {
-    vb = blockIdx.x % nblk;
-    mb = blockIdx.x / nblk;
-  }
-  const int n0 = vb * LM_BN, m0 = mb * BM;
-  f32x16_t acc[TM][TN];
-  // bf16: transposed product, vocab on the MFMA row axis, so a token's 128 logits of this block
-  // sit in registers of one lane pair (see the epilogue below)
-  f32x16_t acct[LM_BN / 64][BM / 64];
-  float ssq[BM / 64];     // per lane: its half of the squared norm of token wc0 + j*32 + (lane&31)
-  if constexpr (FAST && sizeof(T) == 4) {
-    const DenseRows ra{(const bf16_t*)A, 2 * lda, M, m0};
-    const DenseRows rw{(const bf16_t*)W, 2 * K, V, n0};
-#pragma unroll
-    for (int j = 0; j < BM / 64; ++j) ssq[j] = 0.f;
-    if (row_norm)
-      fast_mainloop<LM_BN, BM, 2, 2, 2, 64, true, 0, true>(rw, ra, 0, 2 * K, smem_raw, acct, 0, ssq);
-    else
-      fast_mainloop<LM_BN, BM, 2, 2, 2, 64, false, 0, true>(rw, ra, 0, 2 * K, smem_raw, acct);
-  } else if constexpr (FAST) {
-    const DenseRows ra{(const bf16_t*)A, lda, M, m0};
-    const DenseRows rw{(const bf16_t*)W, K, V, n0};
-#pragma unroll
-    for (int j = 0; j < BM / 64; ++j) ssq[j] = 0.f;
-    if (K % 64 == 0) {
-      if (row_norm)
-        lean_mainloop<LM_BN, BM, 2, 2, 2, 64, true>((const bf16_t*)W, K, V, n0, (const bf16_t*)A,
-                                                    lda, M, m0, K, smem_raw, acct, ssq);
-      else if (xcd_order & 2)   // s_setprio around the MFMA clusters, as gemm_lean_kernel
-        lean_mainloop<LM_BN, BM, 2, 2, 2, 64, false, true>((const bf16_t*)W, K, V, n0,
-                                                           (const bf16_t*)A, lda, M, m0, K,
-                                                           smem_raw, acct);
-      else
-        lean_mainloop<LM_BN, BM, 2, 2, 2, 64>((const bf16_t*)W, K, V, n0, (const bf16_t*)A, lda,
-                                              M, m0, K, smem_raw, acct);
-    } else if (row_norm) {
-      fast_mainloop<LM_BN, BM, 2, 2, 2, 64, true>(rw, ra, 0, K, smem_raw, acct, 0, ssq);
-    } else {
-      fast_mainloop<LM_BN, BM>(rw, ra, 0, K, smem_raw, acct);
-    }
-  } else {
-    DenseA<T, BM> la{A, lda, M, m0};
-    gemm_mainloop<T, BM, LM_BN>(la, W, K, V, n0, 0, K, (T*)smem_raw, acc);
-  }
-  // row norms for get_prefix_tokens (normalize(a) . w == (a . w) / max(||a||, 1e-12)); the
-  // transposed top-1 path gets them from its own B fragments instead (see below)
-  if (row_norm && !FAST) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (int r = wid; r < BM; r += 4) {
-      float s = 0.f;
-      if (m0 + r < M)
-        for (int k = lane; k < K; k += 64) {
-          float a = ldf(A + (long)(m0 + r) * lda + k);
-          s += a * a;
-        }
-      s = wave_sum(s);
-      if (lane == 0) inv_norm[r] = 1.0f / fmaxf(sqrtf(s), 1e-12f);
-    }
-  }
-  __syncthreads();
-  if constexpr (FAST) {
-    // acct[i][j][e]: vocab n0 + wr0 + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5), token
-    // m0 + wc0 + j*32 + (lane&31).  Per token: a descending top-KMAX list and the sum-exp over the
-    // lane's 32 vocab entries in registers, one xor-32 exchange with the partner lane, then the
-    // two waves holding the other 64 vocab rows of the same tokens merge through LDS.  Ties keep
-    // the lower vocab index (torch argmax / topk order).
-    constexpr int TMV = LM_BN / 64, TNT = BM / 64;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wr0 = (wid >> 1) * (LM_BN / 2), wc0 = (wid & 1) * (BM / 2), wg = wid >> 1;
-    float* xm = reinterpret_cast<float*>(smem_raw);          // [2][BM] max
-    float* xs = xm + 2 * BM;                                  // [2][BM] sum-exp
-    float* xv = xs + 2 * BM;                                  // [2][BM][KMAX] top values
-    int* xi = reinterpret_cast<int*>(xv + 2 * BM * KMAX);     // [2][BM][KMAX] top indices
-    auto better = [](float v, int i, float w, int k) { return v > w || (v == w && i < k); };
-#pragma unroll
-    for (int j = 0; j < TNT; ++j) {
-      const int r = wc0 + j * 32 + (lane & 31);                // token within the block
-      float sc = 1.0f;
-      if (row_norm) {
-        const float t = ssq[j] + __shfl_xor(ssq[j], 32, 64);
-        sc = 1.0f / fmaxf(sqrtf(t), 1e-12f);
-      }
-      float tv[KMAX];
-      int ti[KMAX];
-#pragma unroll
-      for (int q = 0; q < KMAX; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
-#pragma unroll
-      for (int i = 0; i < TMV; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-          float cv = n < V ? acct[i][j][e] * sc : -INFINITY;
-          if (tdiv) cv = cv / temp;
-          int ci = n;
-          // n increases with (i, e): a value goes behind its equals (strict >), so the lower
-          // index stays first.  The list is descending, hence lt[q] = cv > tv[q] is monotone in q
-          // and slot q takes cv where lt[q] && !lt[q - 1], its upper neighbour where both hold:
-          // every entry behind the new one moves down one slot whatever it compares to.  (The
-          // earlier bubble compared the DISPLACED entry with strict > against its successor, so
-          // among equals the lower index slid behind the higher one or fell off the list.)
-          // Select-only (per-element branches became ~500 divergent exec-mask branches per
-          // kernel), all compares on the old list; the outer test skips a value no lane keeps
-          if (cv > tv[KMAX - 1]) {
-            bool lt[KMAX];
-#pragma unroll
-            for (int q = 0; q < KMAX; ++q) lt[q] = cv > tv[q];
-#pragma unroll
-            for (int q = KMAX - 1; q >= 1; --q) {
-              tv[q] = lt[q] ? (lt[q - 1] ? tv[q - 1] : cv) : tv[q];
-              ti[q] = lt[q] ? (lt[q - 1] ? ti[q - 1] : ci) : ti[q];
-            }
-            tv[0] = lt[0] ? cv : tv[0];
-            ti[0] = lt[0] ? ci : ti[0];
-          }
-        }
-      // merge with the partner lane's list (both lanes end with the same top-KMAX)
-      float pv[KMAX];
-      int pi[KMAX];
-#pragma unroll
-      for (int q = 0; q < KMAX; ++q) { pv[q] = __shfl_xor(tv[q], 32, 64); pi[q] = __shfl_xor(ti[q], 32, 64); }
-      if constexpr (KMAX > 1) {
-        // merge of two descending lists, select-only: the partner's entries bubble into this
-        // lane's list like new values (the same order as a merge: value desc, then index asc)
-#pragma unroll
-        for (int p = 0; p < KMAX; ++p) {
-          float cv = pv[p];
-          int ci = pi[p];
-#pragma unroll
-          for (int q = 0; q < KMAX; ++q) {
-            const bool c = better(cv, ci, tv[q], ti[q]);
-            const float t = tv[q];
-            const int u = ti[q];
-            tv[q] = c ? cv : t;
-            ti[q] = c ? ci : u;
-            cv = c ? t : cv;
-            ci = c ? u : ci;
-          }
-        }
-      } else {
-        const bool c = better(pv[0], pi[0], tv[0], ti[0]);
-        tv[0] = c ? pv[0] : tv[0];
-        ti[0] = c ? pi[0] : ti[0];
-      }
-      const float bv = tv[0];
-      float se = 0.f;
-      // the softmax denominator only for callers that need log-probabilities (beam search);
-      // greedy argmax and get_prefix_tokens pass part_stat = NULL and skip these 64 exps/lane
-      if (part_stat != nullptr && bv != -INFINITY) {
-#pragma unroll
-        for (int i = 0; i < TMV; ++i)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-            if (n < V) se += __expf((tdiv ? acct[i][j][e] * sc / temp : acct[i][j][e] * sc) - bv);
-          }
-        se += __shfl_xor(se, 32, 64);
-      }
-      if (lane < 32) {
-        xm[wg * BM + r] = bv;
-        xs[wg * BM + r] = se;
-#pragma unroll
-        for (int q = 0; q < KMAX; ++q) {
-          xv[(wg * BM + r) * KMAX + q] = tv[q];
-          xi[(wg * BM + r) * KMAX + q] = ti[q];
-        }
-      }
-    }
-    __syncthreads();
-    for (int r = threadIdx.x; r < BM; r += 256) {
-      const int m = m0 + r;
-      if (m >= M) continue;
-      const float m0v = xm[r], m1v = xm[BM + r];
-      const float g = fmaxf(m0v, m1v);
-      const float se = (m0v == -INFINITY ? 0.f : xs[r] * expf(m0v - g)) +
-                       (m1v == -INFINITY ? 0.f : xs[BM + r] * expf(m1v - g));
-      const long o = (long)m * nblk + vb;
-      if (part_stat != nullptr) {
-        part_stat[o * 2 + 0] = g;
-        part_stat[o * 2 + 1] = se;
-      }
-      const float* l0v = xv + r * KMAX;
-      const int* l0i = xi + r * KMAX;
-      const float* l1v = xv + (BM + r) * KMAX;
-      const int* l1i = xi + (BM + r) * KMAX;
-      int a = 0, b = 0;
-      for (int q = 0; q < topk; ++q) {
-        const bool ta = b >= KMAX || (a < KMAX && better(l0v[a], l0i[a], l1v[b], l1i[b]));
-        part_val[o * topk + q] = ta ? l0v[a] : l1v[b];
-        part_idx[o * topk + q] = ta ? l0i[a] : l1i[b];
-        if (ta) ++a; else ++b;
-      }
-    }
-    return;
-  }
-  float* tile = reinterpret_cast<float*>(smem_raw);   // [BM][LM_BN+1]
-  {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wr0 = (wid >> 1) * (BM / 2), wc0 = (wid & 1) * (LM_BN / 2);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int r = wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-          const int c = wc0 + j * 32 + (lane & 31);
-          tile[r * (LM_BN + 1) + c] = acc[i][j][e];
-        }
-  }
-  __syncthreads();
-  // each row is reduced by TPR threads, each scanning LM_BN/TPR consecutive columns
-  constexpr int TPR = 256 / BM;
-  constexpr int CPT = LM_BN / TPR;
-  const int r = threadIdx.x / TPR, sub = threadIdx.x % TPR;
-  const int m = m0 + r;
-  const float scale = row_norm ? inv_norm[r] : 1.0f;
-  float mx = -INFINITY;
-  float tv[KMAX];
-  int ti[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
-  for (int c = sub * CPT; c < sub * CPT + CPT; ++c) {
-    const int n = n0 + c;
-    if (n >= V) break;
-    float v = tile[r * (LM_BN + 1) + c] * scale;
-    if (tdiv) v = v / temp;
-    mx = fmaxf(mx, v);
-    // insertion into the descending top-k list (strict > keeps the lower index on ties)
-    if (KMAX == 1) {
-      if (v > tv[0]) { tv[0] = v; ti[0] = n; }
-    } else if (v > tv[KMAX - 1]) {
-      // place the new value in the (static-indexed) descending list: select-only, as the
-      // transposed path above (lt[q] is monotone in q; entries behind the new one move down)
-      bool lt[KMAX];
-#pragma unroll
-      for (int q = 0; q < KMAX; ++q) lt[q] = v > tv[q];
-#pragma unroll
-      for (int q = KMAX - 1; q >= 1; --q) {
-        tv[q] = lt[q] ? (lt[q - 1] ? tv[q - 1] : v) : tv[q];
-        ti[q] = lt[q] ? (lt[q - 1] ? ti[q - 1] : n) : ti[q];
-      }
-      tv[0] = lt[0] ? v : tv[0];
-      ti[0] = lt[0] ? n : ti[0];
-    }
-  }
-  // combine max across the TPR threads of this row (consecutive lanes)
-  float gmx = mx;
-#pragma unroll
-  for (int o = 1; o < TPR; o <<= 1) gmx = fmaxf(gmx, __shfl_xor(gmx, o, 64));
-  float se = 0.f;
-  for (int c = sub * CPT; part_stat != nullptr && c < sub * CPT + CPT; ++c) {
-    const int n = n0 + c;
-    if (n >= V) break;
-    se += expf((tdiv ? tile[r * (LM_BN + 1) + c] * scale / temp : tile[r * (LM_BN + 1) + c] * scale) - gmx);
-  }
-#pragma unroll
-  for (int o = 1; o < TPR; o <<= 1) se += __shfl_xor(se, o, 64);
-  __syncthreads();
-  // merge the TPR sorted lists through LDS (reuse the tile area after the barrier)
-  float* mv = reinterpret_cast<float*>(smem_raw);
-  int* mi = reinterpret_cast<int*>(smem_raw + 256 * MAXK * 4);
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q) { mv[threadIdx.x * MAXK + q] = tv[q]; mi[threadIdx.x * MAXK + q] = ti[q]; }
-  __syncthreads();
-  if (sub == 0 && m < M) {
-    const long o = ((long)m * nblk + vb);
-    if (part_stat != nullptr) {
-      part_stat[o * 2 + 0] = gmx;
-      part_stat[o * 2 + 1] = se;
-    }
-    int ptr[TPR];
-#pragma unroll
-    for (int t = 0; t < TPR; ++t) ptr[t] = 0;
-    for (int q = 0; q < topk; ++q) {
-      int best = -1;
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int t = 0; t < TPR; ++t) {
-        if (ptr[t] >= topk) continue;
-        const float v = mv[(threadIdx.x + t) * MAXK + ptr[t]];
-        const int ix = mi[(threadIdx.x + t) * MAXK + ptr[t]];
-        if (best < 0 || v > bv || (v == bv && ix < bi)) { best = t; bv = v; bi = ix; }
-      }
-      ptr[best]++;
-      part_val[o * topk + q] = bv;
-      part_idx[o * topk + q] = bi;
-    }
-  }
-}
-
-// ------------------------------------------------------------------ LM head, teacher-forced
-// Scoring a GIVEN token per row (cross-entropy over the caption tokens: train_prompt.py:133,
-// caption_model.py:297-313): lmhead_kernel's main loops and block order with another register
-// epilogue.  Per (row, 128-column block): the block's max, sum(exp(logit - max)) and top-1
-// (value, index; ties -> lower index) as lmhead_kernel writes them, and -- from the one lane of
-// the one block that holds column tgt[m] -- the target's logit into tgt_logit[m]: one writer per
-// row, no atomics.  No top-k list, no [M][V] logits.  Rows with tgt outside [0, V) write no
-// target logit.  The statistics use lmhead_kernel's arithmetic (__expf, the same merge order), so
-// the log-sum-exp of a row equals the one zs_lmhead_topk's partials give, bit for bit.
-template <typename T, int BM>
-__global__ __launch_bounds__(256) void lmhead_nll_kernel(int xcd_order, int M, int K, int V,
-                                                         const T* A, int lda, const T* W,
-                                                         const int* __restrict__ tgt,
-                                                         float* __restrict__ part_stat,
-                                                         float* __restrict__ part_val,
-                                                         int* __restrict__ part_idx,
-                                                         float* __restrict__ tgt_logit) {
-  constexpr int SM_LOOP = 2 * FastTile<BM, LM_BN>::STAGE;   // 4 waves (2x2), 2 stages
-  static_assert(2 * BM * 3 * 4 <= SM_LOOP, "epilogue exchange fits the ring's LDS");
-  __shared__ __attribute__((aligned(16))) char smem_raw[SM_LOOP];
-  // XCD-local block order: see lmhead_kernel
-  const int ntm = cdiv(M, BM), nblk = cdiv(V, LM_BN), nwg = nblk * ntm;
-  int vb, mb;
-  if (xcd_order & 1) {
-    const int b = blockIdx.x, x = b & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (b >> 3);
-    vb = u / ntm;
-    mb = u - vb * ntm;
-  } else {
-    vb = blockIdx.x % nblk;
-    mb = blockIdx.x / nblk;
-  }
-  const int n0 = vb * LM_BN, m0 = mb * BM;
-  // transposed product (vocab on the MFMA row axis), as lmhead_kernel's ring paths
-  f32x16_t acct[LM_BN / 64][BM / 64];
-  if constexpr (sizeof(T) == 4) {
-    const DenseRows ra{(const bf16_t*)A, 2 * lda, M, m0};
-    const DenseRows rw{(const bf16_t*)W, 2 * K, V, n0};
-    fast_mainloop<LM_BN, BM, 2, 2, 2, 64, false, 0, true>(rw, ra, 0, 2 * K, smem_raw, acct);
-  } else if (K % 64 == 0) {
-    if (xcd_order & 2)
-      lean_mainloop<LM_BN, BM, 2, 2, 2, 64, false, true>((const bf16_t*)W, K, V, n0,
-                                                         (const bf16_t*)A, lda, M, m0, K,
-                                                         smem_raw, acct);
-    else
-      lean_mainloop<LM_BN, BM, 2, 2, 2, 64>((const bf16_t*)W, K, V, n0, (const bf16_t*)A, lda, M,
-                                            m0, K, smem_raw, acct);
-  } else {
-    const DenseRows ra{(const bf16_t*)A, lda, M, m0};
-    const DenseRows rw{(const bf16_t*)W, K, V, n0};
-    fast_mainloop<LM_BN, BM>(rw, ra, 0, K, smem_raw, acct);
-  }
-  __syncthreads();
-  // acct[i][j][e]: vocab n0 + wr0 + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5), token
-  // m0 + wc0 + j*32 + (lane&31): a token's 64 logits of this wave sit in one lane pair
-  constexpr int TMV = LM_BN / 64, TNT = BM / 64;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr0 = (wid >> 1) * (LM_BN / 2), wc0 = (wid & 1) * (BM / 2), wg = wid >> 1;
-  float* xm = reinterpret_cast<float*>(smem_raw);          // [2][BM] max
-  float* xs = xm + 2 * BM;                                  // [2][BM] sum-exp
-  int* xi = reinterpret_cast<int*>(xs + 2 * BM);            // [2][BM] argmax
-#pragma unroll
-  for (int j = 0; j < TNT; ++j) {
-    const int r = wc0 + j * 32 + (lane & 31);                // token within the block
-    const int m = m0 + r;
-    const int t = m < M ? tgt[m] : -1;
-    float bv = -INFINITY, tl = 0.f;
-    int bi = 0x7fffffff;
-    bool hit = false;
-#pragma unroll
-    for (int i = 0; i < TMV; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        const float cv = n < V ? acct[i][j][e] : -INFINITY;
-        const bool c = cv > bv;        // n increases with (i, e): strict > keeps the lower index
-        bv = c ? cv : bv;
-        bi = c ? n : bi;
-        const bool h = n == t && n < V;
-        tl = h ? acct[i][j][e] : tl;
-        hit = hit || h;
-      }
-    if (hit) tgt_logit[m] = tl;        // t >= 0 here, so m < M
-    {
-      const float pv = __shfl_xor(bv, 32, 64);
-      const int pi = __shfl_xor(bi, 32, 64);
-      const bool c = pv > bv || (pv == bv && pi < bi);
-      bv = c ? pv : bv;
-      bi = c ? pi : bi;
-    }
-    float se = 0.f;
-    if (bv != -INFINITY) {
-#pragma unroll
-      for (int i = 0; i < TMV; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-          if (n < V) se += __expf(acct[i][j][e] - bv);
-        }
-      se += __shfl_xor(se, 32, 64);
-    }
-    if (lane < 32) {
-      xm[wg * BM + r] = bv;
-      xs[wg * BM + r] = se;
-      xi[wg * BM + r] = bi;
-    }
-  }
-  __syncthreads();
-  // the two wave rows hold vocab halves [0, 64) and [64, 128) of the block: merge
-  for (int r = threadIdx.x; r < BM; r += 256) {
-    const int m = m0 + r;
-    if (m >= M) continue;
-    const float m0v = xm[r], m1v = xm[BM + r];
-    const float g = fmaxf(m0v, m1v);
-    const float se = (m0v == -INFINITY ? 0.f : xs[r] * expf(m0v - g)) +
-                     (m1v == -INFINITY ? 0.f : xs[BM + r] * expf(m1v - g));
-    const long o = (long)m * nblk + vb;
-    part_stat[o * 2 + 0] = g;
-    part_stat[o * 2 + 1] = se;
-    const bool hi = m1v > m0v;         // equal: the lower half's (lower) index
-    part_val[o] = hi ? m1v : m0v;
-    part_idx[o] = hi ? xi[BM + r] : xi[r];
-  }
-}
-
-// ------------------------------------------------------------------ similarity rank (retrieval)
-// Retrieval metrics (a2t / t2a, retrieval/tools/utils.py:169-251) need, per query row m and target
-// column j = tgt[m][t], the position of j in the row sorted by similarity: rank = #{n : sim[m][n] >
-// sim[m][j]} + #{n < j : sim[m][n] == sim[m][j]} (value descending, then index ascending).
-// lmhead_nll_kernel's main loops, block order and tiles with another register epilogue, launched
-// twice so that every compared value -- the target's own included -- comes out of the same MFMA
-// chain (an exact duplicate of the target row then compares EQUAL, whatever the rounding):
-//   PASS 0  only the blocks whose 128 columns hold a target of one of their rows run the main
-//           loop; the one lane that holds column tgt[m][t] writes tgt_sim[m][t] (one writer per
-//           slot up to equal targets, which write the same bits).
-//   PASS 1  every block counts, per (row, t), its columns that sort before the target; the lane
-//           pair and the two wave rows are summed in registers / LDS and ONE integer atomicAdd per
-//           (row, t, block) with a non-zero count goes to rank[m][t].  Integer sums commute: the
-//           result does not depend on the order of the blocks.  No [M][N] matrix, no partials.
-// Targets outside [0, N) count nothing (sim_rank_init_kernel has set their rank to -1).
-__global__ void sim_rank_init_kernel(long total, int N, const int* __restrict__ tgt,
-                                     float* __restrict__ tgt_sim, int* __restrict__ rank) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int j = tgt[i];
-  const bool ok = j >= 0 && j < N;
-  rank[i] = ok ? 0 : -1;
-  if (!ok) tgt_sim[i] = 0.f;
-}
-
-template <typename T, int BM, int PASS>
-__global__ __launch_bounds__(256) void sim_rank_kernel(int xcd_order, int M, int K, int N,
-                                                       const T* Q, int ldq, const T* G, int ldg,
-                                                       const int* __restrict__ tgt, int TT,
-                                                       float* __restrict__ tgt_sim,
-                                                       int* __restrict__ rank) {
-  constexpr int SM_LOOP = 2 * FastTile<BM, LM_BN>::STAGE;   // 4 waves (2x2), 2 stages
-  static_assert(BM * MAXK * 4 <= SM_LOOP, "epilogue exchange fits the ring's LDS");
-  __shared__ __attribute__((aligned(16))) char smem_raw[SM_LOOP];
-  // XCD-local block order: see lmhead_kernel
-  const int ntm = cdiv(M, BM), nblk = cdiv(N, LM_BN), nwg = nblk * ntm;
-  int vb, mb;
-  if (xcd_order & 1) {
-    const int b = blockIdx.x, x = b & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int u = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (b >> 3);
-    vb = u / ntm;
-    mb = u - vb * ntm;
-  } else {
-    vb = blockIdx.x % nblk;
-    mb = blockIdx.x / nblk;
-  }
-  const int n0 = vb * LM_BN, m0 = mb * BM;
-  if constexpr (PASS == 0) {
-    // a block none of whose rows has a target in its columns has nothing to store
-    // (the vote goes through the ring's own LDS: ONE __shared__ array, as lmhead_kernel)
-    int* flag = reinterpret_cast<int*>(smem_raw);
-    if (threadIdx.x == 0) *flag = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < BM * TT; i += 256) {
-      const int m = m0 + i / TT;
-      if (m < M) {
-        const int j = tgt[(long)m0 * TT + i];
-        if (j >= n0 && j < n0 + LM_BN && j < N) *flag = 1;
-      }
-    }
-    __syncthreads();
-    const int any = *flag;
-    __syncthreads();                                   // read before the main loop's DMA lands
-    if (!any) return;
-  }
-  // transposed product (gallery on the MFMA row axis), as lmhead_nll_kernel
-  f32x16_t acct[LM_BN / 64][BM / 64];
-  if constexpr (sizeof(T) == 4) {
-    const DenseRows ra{(const bf16_t*)Q, 2 * ldq, M, m0};
-    const DenseRows rw{(const bf16_t*)G, 2 * ldg, N, n0};
-    fast_mainloop<LM_BN, BM, 2, 2, 2, 64, false, 0, true>(rw, ra, 0, 2 * K, smem_raw, acct);
-  } else if (K % 64 == 0) {
-    if (xcd_order & 2)
-      lean_mainloop<LM_BN, BM, 2, 2, 2, 64, false, true>((const bf16_t*)G, ldg, N, n0,
-                                                         (const bf16_t*)Q, ldq, M, m0, K,
-                                                         smem_raw, acct);
-    else
-      lean_mainloop<LM_BN, BM, 2, 2, 2, 64>((const bf16_t*)G, ldg, N, n0, (const bf16_t*)Q, ldq, M,
-                                            m0, K, smem_raw, acct);
-  } else {
-    const DenseRows ra{(const bf16_t*)Q, ldq, M, m0};
-    const DenseRows rw{(const bf16_t*)G, ldg, N, n0};
-    fast_mainloop<LM_BN, BM>(rw, ra, 0, K, smem_raw, acct);
-  }
-  __syncthreads();
-  // acct[i][j][e]: column n0 + wr0 + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5), query
-  // m0 + wc0 + j*32 + (lane&31): a query's 64 similarities of this wave sit in one lane pair
-  constexpr int TMV = LM_BN / 64, TNT = BM / 64;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr0 = (wid >> 1) * (LM_BN / 2), wc0 = (wid & 1) * (BM / 2), wg = wid >> 1;
-  int* xc = reinterpret_cast<int*>(smem_raw);               // [BM][MAXK] counts of wave row 1
-  int cnt[TNT][MAXK];
-#pragma unroll
-  for (int j = 0; j < TNT; ++j) {
-    const int r = wc0 + j * 32 + (lane & 31);                // query within the block
-    const int m = m0 + r;
-    int tj[MAXK];
-    float ts[MAXK];
-#pragma unroll
-    for (int t = 0; t < MAXK; ++t) {
-      cnt[j][t] = 0;
-      tj[t] = -1;
-      ts[t] = INFINITY;
-      if (t < TT && m < M) {
-        const int c = tgt[(long)m * TT + t];
-        if (c >= 0 && c < N) {
-          tj[t] = c;
-          if constexpr (PASS == 1) ts[t] = tgt_sim[(long)m * TT + t];
-        }
-      }
-    }
-    if constexpr (PASS == 0) {
-#pragma unroll
-      for (int t = 0; t < MAXK; ++t) {
-        if (t >= TT) break;                                  // uniform
-        // which accumulator element of THIS lane holds column tj, if any: invert
-        // n = n0 + wr0 + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5)
-        const int rel = tj[t] - n0 - wr0;                    // tj < N, so a hit is a real column
-        const bool mine = tj[t] >= 0 && rel >= 0 && rel < LM_BN / 2 && ((rel >> 2) & 1) == (lane >> 5);
-        const int slot = mine ? (rel >> 5) * 16 + (rel & 3) + 4 * ((rel & 31) >> 3) : -1;
-        float v = 0.f;
-#pragma unroll
-        for (int i = 0; i < TMV; ++i)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) v = slot == i * 16 + e ? acct[i][j][e] : v;
-        if (mine) tgt_sim[(long)m * TT + t] = v;             // tj >= 0 here, so m < M
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < MAXK; ++t) {
-        if (t >= TT) break;                                  // uniform
-        int c = 0;
-#pragma unroll
-        for (int i = 0; i < TMV; ++i)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int n = n0 + wr0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-            const float cv = acct[i][j][e];
-            // before the target: a greater value, or an equal one at a lower index (n == tj
-            // itself is neither); padding columns n >= N are not counted
-            c += (n < N && (cv > ts[t] || (cv == ts[t] && n < tj[t]))) ? 1 : 0;
-          }
-        cnt[j][t] = c + __shfl_xor(c, 32, 64);
-      }
-    }
-  }
-  if constexpr (PASS == 1) {
-    // the two wave rows hold column halves [0, 64) and [64, 128) of the block: add, then one
-    // integer atomic per (query, t) of this block
-    if (wg == 1 && lane < 32) {
-#pragma unroll
-      for (int j = 0; j < TNT; ++j)
-#pragma unroll
-        for (int t = 0; t < MAXK; ++t) xc[(wc0 + j * 32 + lane) * MAXK + t] = cnt[j][t];
-    }
-    __syncthreads();
-    if (wg == 0 && lane < 32) {
-#pragma unroll
-      for (int j = 0; j < TNT; ++j) {
-        const int r = wc0 + j * 32 + lane;
-        const int m = m0 + r;
-#pragma unroll
-        for (int t = 0; t < MAXK; ++t) {
-          const int c = cnt[j][t] + xc[r * MAXK + t];
-          if (t < TT && m < M && c != 0) atomicAdd(rank + (long)m * TT + t, c);
-        }
-      }
-    }
-  }
-}
-
 }  // namespace zs
 
 using namespace zs;
@@ -1507,130 +882,5 @@ extern "C" int zs_gemm(int M, int N, int K, int dtype, const void* A, int lda, c
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, g);
     ZS_LAUNCH_CHECK();
   }
-  return 0;
-}
-
-extern "C" int zs_lmhead_nblk(int V) { return cdiv(V, LM_BN); }
-
-extern "C" int zs_lmhead_topk(int M, int K, int V, int dtype, const void* A, int lda,
-                              const void* W, int topk, int row_norm, float* part_stat,
-                              float* part_val, int* part_idx, void* stream) {
-  return zs_lmhead_topk_t(M, K, V, dtype, A, lda, W, topk, row_norm, 1.0f, part_stat, part_val,
-                          part_idx, stream);
-}
-
-extern "C" int zs_lmhead_topk_t(int M, int K, int V, int dtype, const void* A, int lda,
-                                const void* W, int topk, int row_norm, float temperature,
-                                float* part_stat, float* part_val, int* part_idx, void* stream) {
-  ZS_REQUIRE(temperature > 0.f, "zs_lmhead_topk_t: temperature %g (> 0)", temperature);
-  ZS_REQUIRE(!row_norm || temperature == 1.0f, "zs_lmhead_topk_t: row_norm with temperature");
-  ZS_REQUIRE(M > 0 && K > 0 && V > 0, "zs_lmhead_topk: bad shape");
-  ZS_REQUIRE(K % BK == 0 && lda % 8 == 0 && lda >= K, "zs_lmhead_topk: K %% 32, lda %% 8, lda >= K");
-  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_lmhead_topk: dtype");
-  ZS_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
-             "zs_lmhead_topk: A and W must be 16-byte aligned");
-  ZS_REQUIRE(topk >= 1 && topk <= MAXK, "zs_lmhead_topk: 1 <= topk <= 8");
-  hipStream_t st = S(stream);
-  const int nblk = cdiv(V, LM_BN);
-  // f32 on the LDS-DMA ring when its 16-byte rows allow (lda % 4 already holds: lda % 8)
-  const bool ring = dtype != ZS_BF16 && g_f32_fast && K % 4 == 0;
-#define LMH(T, BM_, KM_)                                                                     \
-  do {                                                                                       \
-    if (sizeof(T) == 4 && ring)                                                              \
-      hipLaunchKernelGGL((lmhead_kernel<T, BM_, KM_, true>), dim3(nblk * cdiv(M, BM_)), dim3(256), \
-                         0, st, (g_fast_xcd ? 1 : 0) | (g_lm_prio ? 2 : 0), M, K, V, (const T*)A, \
-                         lda, (const T*)W, topk, row_norm, part_stat, part_val, part_idx,       \
-                         temperature);                                                       \
-    else                                                                                     \
-      hipLaunchKernelGGL((lmhead_kernel<T, BM_, KM_>), dim3(nblk * cdiv(M, BM_)), dim3(256), 0, \
-                         st, (g_fast_xcd ? 1 : 0) | (g_lm_prio ? 2 : 0), M, K, V, (const T*)A,  \
-                         lda, (const T*)W, topk, row_norm, part_stat, part_val, part_idx,       \
-                         temperature);                                                       \
-  } while (0)
-  // top-k lists of 1 (argmax), 5 (beam <= 5: generate_beam's default) or 8 entries per block
-#define LMH_K(T, BM_)                                                                          \
-  do {                                                                                         \
-    if (topk == 1) LMH(T, BM_, 1);                                                             \
-    else if (topk <= 5) LMH(T, BM_, 5);                                                        \
-    else LMH(T, BM_, 8);                                                                       \
-  } while (0)
-  if (M <= 64) {
-    if (dtype == ZS_BF16) LMH_K(bf16_t, 64); else LMH_K(float, 64);
-  } else {
-    if (dtype == ZS_BF16) LMH_K(bf16_t, 128); else LMH_K(float, 128);
-  }
-#undef LMH_K
-#undef LMH
-  ZS_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int zs_lmhead_nll(int M, int K, int V, int dtype, const void* A, int lda,
-                             const void* W, const int* tgt, float* part_stat, float* part_val,
-                             int* part_idx, float* tgt_logit, void* stream) {
-  ZS_REQUIRE(M > 0 && K > 0 && V > 0, "zs_lmhead_nll: bad shape");
-  ZS_REQUIRE(K % BK == 0 && lda % 8 == 0 && lda >= K, "zs_lmhead_nll: K %% 32, lda %% 8, lda >= K");
-  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_lmhead_nll: dtype");
-  ZS_REQUIRE(A && W && tgt && part_stat && part_val && part_idx && tgt_logit,
-             "zs_lmhead_nll: null pointer");
-  ZS_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
-             "zs_lmhead_nll: A and W must be 16-byte aligned");
-  hipStream_t st = S(stream);
-  const int nblk = cdiv(V, LM_BN);
-  const int order = (g_fast_xcd ? 1 : 0) | (g_lm_prio ? 2 : 0);
-#define LMN(T, BM_)                                                                            \
-  hipLaunchKernelGGL((lmhead_nll_kernel<T, BM_>), dim3(nblk * cdiv(M, BM_)), dim3(256), 0, st, \
-                     order, M, K, V, (const T*)A, lda, (const T*)W, tgt, part_stat, part_val,  \
-                     part_idx, tgt_logit)
-  // the row tiles of zs_lmhead_topk: 64 rows up to M = 64, 128 above
-  if (M <= 64) {
-    if (dtype == ZS_BF16) LMN(bf16_t, 64); else LMN(float, 64);
-  } else {
-    if (dtype == ZS_BF16) LMN(bf16_t, 128); else LMN(float, 128);
-  }
-#undef LMN
-  ZS_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int zs_sim_rank(int M, int N, int K, int dtype, const void* Q, int ldq, const void* G,
-                           int ldg, const int* tgt, int T, float* tgt_sim, int* rank,
-                           void* stream) {
-  ZS_REQUIRE(M > 0 && N > 0 && K > 0, "zs_sim_rank: bad shape");
-  ZS_REQUIRE(K % BK == 0 && ldq % 8 == 0 && ldg % 8 == 0 && ldq >= K && ldg >= K,
-             "zs_sim_rank: K %% 32, ldq / ldg %% 8 and >= K");
-  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_sim_rank: dtype");
-  ZS_REQUIRE(T >= 1 && T <= MAXK, "zs_sim_rank: 1 <= T <= 8");
-  ZS_REQUIRE(Q && G && tgt && tgt_sim && rank, "zs_sim_rank: null pointer");
-  ZS_REQUIRE(((uintptr_t)Q & 15) == 0 && ((uintptr_t)G & 15) == 0,
-             "zs_sim_rank: Q and G must be 16-byte aligned");
-  const long total = (long)M * T;
-  const int nblk = cdiv(N, LM_BN);
-  // M x T and the 1-D grid of the 64-row tile must fit an int
-  ZS_REQUIRE(total < (1L << 31) && (long)nblk * cdiv(M, 64) < (1L << 31),
-             "zs_sim_rank: M x T or the grid does not fit an int");
-  hipStream_t st = S(stream);
-  const int order = (g_fast_xcd ? 1 : 0) | (g_lm_prio ? 2 : 0);
-  hipLaunchKernelGGL(sim_rank_init_kernel, dim3((unsigned)cdiv(total, 256L)), dim3(256), 0, st,
-                     total, N, tgt, tgt_sim, rank);
-  ZS_LAUNCH_CHECK();
-#define SRK(T_, BM_, P_)                                                                        \
-  hipLaunchKernelGGL((sim_rank_kernel<T_, BM_, P_>), dim3(nblk * cdiv(M, BM_)), dim3(256), 0, st, \
-                     order, M, K, N, (const T_*)Q, ldq, (const T_*)G, ldg, tgt, T, tgt_sim, rank)
-#define SRK2(T_, BM_)                                                                           \
-  do {                                                                                          \
-    SRK(T_, BM_, 0);                                                                            \
-    ZS_LAUNCH_CHECK();                                                                          \
-    SRK(T_, BM_, 1);                                                                            \
-  } while (0)
-  // the row tiles of zs_lmhead_nll: 64 rows up to M = 64, 128 above
-  if (M <= 64) {
-    if (dtype == ZS_BF16) SRK2(bf16_t, 64); else SRK2(float, 64);
-  } else {
-    if (dtype == ZS_BF16) SRK2(bf16_t, 128); else SRK2(float, 128);
-  }
-#undef SRK2
-#undef SRK
-  ZS_LAUNCH_CHECK();
   return 0;
 }

@@ -1,4 +1,4 @@
-// MFMA GEMM core shared by gemm.hip (Linear / LM head) and cnn.hip (implicit-GEMM conv3x3).
+// MFMA GEMM core shared by gemm.hip (Linear), lmhead.hip (the f32 LM-head tile kernel) and cnn.hip (implicit-GEMM conv3x3).
 // See gemm.hip for the tiling description.
 #pragma once
 #include "common.h"

@@ -231,8 +231,8 @@ __device__ __forceinline__ void fast_mainloop(
   __syncthreads();   // callers may reuse the LDS for the epilogue
 }
 
-// Lean variant of the ring (gemm_lean_kernel, lmhead_kernel): the per-lane DMA source pointers
-// of the tile's A rows [m0, m0+BM) and W rows [n0, n0+BN) are computed once (rows clamped into
+// Lean variant of the ring (gemm_lean_kernel, lmhead.hip's transposed_product): the per-lane DMA
+// source pointers of the tile's A rows [m0, m0+BM) and W rows [n0, n0+BN) are computed once (rows clamped into
 // the matrices; clamped rows only feed outputs the caller's store guard drops) and K % BK == 0,
 // so a k-step carries just the counted wait, the raw barrier, IPW pointer adds + DMAs and the
 // MFMAs (fast_mainloop's per-chunk zero-chunk selects and 64-bit row products are gone).

@@ -253,7 +253,7 @@ extern int g_lean96;        // gemm.hip
 extern int g_lean8w;        // gemm.hip
 extern int g_lean_min128;    // gemm.hip
 extern int g_lean128_ns;     // gemm.hip
-extern int g_lm_prio;       // gemm.hip
+extern int g_lm_prio;       // lmhead.hip
 extern int g_gemm_rows;     // gemm_rows.hip
 extern int g_rows_nt48;     // gemm_rows.hip
 extern int g_fp8_tile;      // mistral.hip
