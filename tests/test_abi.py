@@ -64,6 +64,26 @@ def test_load_and_error_path(libpath):
     assert lib.zs_lmhead_nblk(50257) == 393
 
 
+def test_tune_set_decode_attn5_admits_only_live_values(libpath):
+    """The decode_attn5 knob selects decode_attn6_kernel's phase length and reductions: 2, 3, 4
+    and 6.  The values whose kernels are retired (0, 1, 5) and an unknown one (7) fail with
+    ZS_ERR_ARG and a message naming the value; the knob is left at its default 6."""
+    from zsaac import _lib
+    lib = _lib.lib()
+    try:
+        for v in (0, 1, 5, 7):
+            with pytest.raises(_lib.ZsError, match=rf"decode_attn5 = {v}\b"):
+                _lib.call("zs_tune_set", b"decode_attn5", v)
+            assert lib.zs_tune_set(b"decode_attn5", v) == -1          # ZS_ERR_ARG
+        for v in (0, 1, 5):
+            lib.zs_tune_set(b"decode_attn5", v)
+            assert "retired" in _lib.last_error()
+        for v in (2, 3, 4, 6):
+            assert _lib.call("zs_tune_set", b"decode_attn5", v) == 0
+    finally:
+        _lib.call("zs_tune_set", b"decode_attn5", 6)
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from zsaac import ops

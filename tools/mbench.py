@@ -440,8 +440,8 @@ def bench_decode_gemm():
 
 
 def bench_attn():
-    """Decode attention at the bench's decode shape (2048 rows x 12 heads, Lmax 102): attn6 /
-    attn5 / LDS-staged, HBM GB/s of the K/V bytes read."""
+    """Decode attention at the bench's decode shape (2048 rows x 12 heads, Lmax 102): the
+    decode_attn5 knob's phase lengths of decode_attn6_kernel, HBM GB/s of the K/V bytes read."""
     from zsaac import ops
     from zsaac._lib import call
     dev = torch.device("cuda", 0)
@@ -454,10 +454,10 @@ def bench_attn():
         pos = torch.full((R,), L - 1, device=dev, dtype=torch.int32)
         byts = R * H * L * 64 * 2 * 2
         r = {}
-        for v in [int(x) for x in os.environ.get("ZS_VARIANTS", "3,2,1").split(",")]:
+        for v in [int(x) for x in os.environ.get("ZS_VARIANTS", "6,4,3,2").split(",")]:
             call("zs_tune_set", b"decode_attn5", v)
             r[v] = timeit(lambda: ops.decode_attention(qkv, R, D, H, kc, vc, Lmax, pos, out), reps=20)
-        call("zs_tune_set", b"decode_attn5", 2)
+        call("zs_tune_set", b"decode_attn5", 6)
         print(f"decode_attn R={R} L={L}: " + "  ".join(
             f"v{v}={t:7.2f}us ({byts / t / 1e3:5.0f} GB/s)" for v, t in r.items()), flush=True)
     x = torch.randn(R, 768, device=dev)
@@ -512,8 +512,7 @@ def bench_attn_beam():
     clip = torch.arange(R, device=dev) // beam
     kvrow = (clip[:, None] * beam + torch.randint(0, beam, (R, Lmax), device=dev)).int().contiguous()
     arms = [("v4", {"decode_attn5": 4}), ("v4_noxcd", {"decode_attn5": 4, "beam_xcd": 1}),
-            ("v3", {"decode_attn5": 3}), ("v2", {"decode_attn5": 2}),
-            ("v5", {"decode_attn5": 5}), ("v6", {"decode_attn5": 6}),
+            ("v3", {"decode_attn5": 3}), ("v2", {"decode_attn5": 2}), ("v6", {"decode_attn5": 6}),
             ("small128", {"small_rmax": 4096, "attn_split": 0}),
             ("small_s1", {"small_rmax": 4096, "attn_split": 1}),
             ("small_s3", {"small_rmax": 4096, "attn_split": 3})]

@@ -9,12 +9,16 @@
 
 namespace zs {
 
-int g_small_attn = 1;     // R <= 128: decode_attn6 with 128-key phases
+int g_small_attn = 1;     // zs_tune_set("small_attn", 0): no small-R decode attention plans
 int g_small_rmax = 128;   // zs_tune_set("small_rmax", r): the row count up to which the small-R
-                          // decode attention kernels are taken
+                          // decode attention plans (attn_split) are taken
 int g_beam_xcd = 5;       // zs_tune_set("beam_xcd", g): beam-row groups per XCD (1 = off)
-int g_decode_attn5 = 6;   // 6: decode_attn6 16-key phases, DPP reductions; 5: + next-phase prefetch; 4/3/2: decode_attn6 (phases of 16/32/64 keys), 1: decode_attn5, 0: LDS
-int g_window_mfma = 1;    // zs_tune_set("window_mfma", 0): VALU window attention for bf16   // zs_tune_set("decode_attn5", 0): LDS-staged decode_attn4 for bf16
+// zs_tune_set("decode_attn5", v): the phase length and the reductions of decode_attn6_kernel above
+// small_rmax rows and in every rowmap call: 6 = 16-key phases with DPP reductions, 4 / 3 / 2 =
+// phases of 16 / 32 / 64 keys with ds_bpermute shuffles.  (The values 0, 1 and 5 chose kernels
+// that are gone; zs_tune_set rejects them.)
+int g_decode_attn5 = 6;
+int g_window_mfma = 1;    // zs_tune_set("window_mfma", 0): VALU window attention for bf16
 
 // ------------------------------------------------------------------ HTSAT window attention
 // grid (B * nWh * nWw, heads), block 64: thread i = token i of the 8x8 window.
@@ -418,6 +422,9 @@ int g_attn_split = 3;   // zs_tune_set("attn_split", v) at R <= 128: 0 one wave 
 int g_row_mfma = 1;   // zs_tune_set("row_mfma", 0): the scalar row_attn_kernel for bf16 too
 
 // ------------------------------------------------------------------ GPT-2 decode attention
+// decode_attn6_kernel (below) is the decode attention; decode_attn4_kernel (Lmax <= 512) and
+// decode_attn_kernel (any Lmax) remain for the f32 calls that have no decode_attn6 plan.
+//
 // grid (R, heads), block 256 (hd == 64): append k/v of the new token at pos[r], then attend
 // 0..pos[r].  The row's K block ([pos][64], contiguous per (row, head) in the cache) is staged
 // into LDS with 16-byte coalesced loads, one thread per key computes its score from LDS, the
@@ -498,137 +505,21 @@ __global__ __launch_bounds__(256) void decode_attn4_kernel(const T* __restrict__
         (po[lane] + po[64 + lane] + po[128 + lane] + po[192 + lane]) * inv);
 }
 
-// Register-resident decode attention (bf16, Lmax <= DA5_MAXK): one wave per (row, head), 4 heads
-// of a row per block.  A lane owns 8 head dims (one 16-byte chunk) of key j = 8*i + lane/8, so one
-// wave-instruction reads 8 consecutive cached keys = 1 KiB contiguous (the cache is
-// [row][head][pos][64]); every K and V load of the row is issued up front (no LDS, no barrier),
-// the q.k partial is reduced over the key's 8 lanes (xor 1,2,4), the softmax statistics and the
-// P.V partials over the 8 key groups (xor 8,16,32).  The new token's k/v (position pos[r]) comes
-// from the qkv row in registers and is written to the cache for later steps.  HBM-bound on the
-// K/V bytes: 2 * (pos+1) * 64 * 2 B per (row, head).
-constexpr int DA5_MAXI = 16;                 // key groups of 8 -> up to 128 positions
-template <typename T>
-__global__ __launch_bounds__(256) void decode_attn5_kernel(const T* __restrict__ qkv, int D,
-                                                           int heads, T* __restrict__ kc,
-                                                           T* __restrict__ vc, int Lmax,
-                                                           const int* __restrict__ pos,
-                                                           const int* __restrict__ kvrow,
-                                                           T* __restrict__ out,
-                                                           const int* __restrict__ rowmap,
-                                                           int nphys) {
-  static_assert(sizeof(T) == 2, "bf16 only");
-  constexpr int HD = 64, EPC = 8;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = blockIdx.x, h = blockIdx.y * 4 + wid;   // c: compact row of qkv / out
-  if (h >= heads) return;
-  const int grp = lane >> 3, sub = lane & 7;
-  const int r = rowmap ? rowmap[c] : c;                  // r: physical row of pos / cache
-  if (r >= nphys) {                                      // padding slot of a compacted step
-    if (grp == 0)
-      *reinterpret_cast<uint4*>(out + (long)c * D + h * HD + sub * EPC) = make_uint4(0, 0, 0, 0);
-    return;
-  }
-  const int p = min(pos[r], Lmax - 1);
-  const T* row = qkv + (long)c * 3 * D + h * HD + sub * EPC;
-  const uint4 qu = *reinterpret_cast<const uint4*>(row);
-  const uint4 knu = *reinterpret_cast<const uint4*>(row + D);
-  const uint4 vnu = *reinterpret_cast<const uint4*>(row + 2 * D);
-  const long rh = ((long)r * heads + h) * Lmax;
-  if (grp == 0) {        // append this step's k/v to the cache
-    *reinterpret_cast<uint4*>(kc + (rh + p) * HD + sub * EPC) = knu;
-    *reinterpret_cast<uint4*>(vc + (rh + p) * HD + sub * EPC) = vnu;
-  }
-  float q[EPC];
-  {
-    const T* e = reinterpret_cast<const T*>(&qu);
-#pragma unroll
-    for (int t = 0; t < EPC; ++t) q[t] = ldf(e + t) * 0.125f;   // 1/sqrt(64), exact
-  }
-  const int nI = (p + 1 + 7) >> 3;
-  uint4 kr[DA5_MAXI], vr[DA5_MAXI];
-#pragma unroll
-  for (int i = 0; i < DA5_MAXI; ++i) {
-    const int j = i * 8 + grp;
-    kr[i] = make_uint4(0, 0, 0, 0);
-    vr[i] = make_uint4(0, 0, 0, 0);
-    if (i < nI && j < p) {
-      const long src = kvrow ? ((long)kvrow[(long)r * Lmax + j] * heads + h) * Lmax : rh;
-      kr[i] = *reinterpret_cast<const uint4*>(kc + (src + j) * HD + sub * EPC);
-      vr[i] = *reinterpret_cast<const uint4*>(vc + (src + j) * HD + sub * EPC);
-    } else if (j == p) {
-      kr[i] = knu;
-      vr[i] = vnu;
-    }
-  }
-  float sc[DA5_MAXI];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < DA5_MAXI; ++i) {
-    const T* e = reinterpret_cast<const T*>(&kr[i]);
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < EPC; ++t) s += q[t] * ldf(e + t);
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    sc[i] = (i * 8 + grp <= p) ? s : -INFINITY;
-    mx = fmaxf(mx, sc[i]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 8, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f, o[EPC];
-#pragma unroll
-  for (int t = 0; t < EPC; ++t) o[t] = 0.f;
-#pragma unroll
-  for (int i = 0; i < DA5_MAXI; ++i) {
-    const float e = (i * 8 + grp <= p) ? expf(sc[i] - mx) : 0.f;
-    sum += e;
-    const T* v = reinterpret_cast<const T*>(&vr[i]);
-#pragma unroll
-    for (int t = 0; t < EPC; ++t) o[t] += e * ldf(v + t);
-  }
-#pragma unroll
-  for (int d = 8; d < 64; d <<= 1) {
-    sum += __shfl_xor(sum, d, 64);
-#pragma unroll
-    for (int t = 0; t < EPC; ++t) o[t] += __shfl_xor(o[t], d, 64);
-  }
-  if (grp == 0) {
-    const float inv = 1.0f / sum;
-    uint4 ou;
-    T* oe = reinterpret_cast<T*>(&ou);
-#pragma unroll
-    for (int t = 0; t < EPC; ++t) stf(oe + t, o[t] * inv);
-    *reinterpret_cast<uint4*>(out + (long)c * D + h * HD + sub * EPC) = ou;
-  }
-}
+// decode_attn6: one wave per (row, head), 4 heads of a row per block, everything in registers
+// (no LDS, no barrier).  A lane owns 8 head dims (one 16-byte chunk) of key j = 8*i + lane/8, so
+// one wave-instruction reads 8 consecutive cached keys = 1 KiB contiguous (the cache is
+// [row][head][pos][64]).  The keys are taken in phases of KPP (KPP / 8 key groups x 8 keys, one
+// wave-load per group each for K and V) with an online softmax across phases, so a wave holds one
+// phase's K/V in registers (~100 VGPRs at 64 keys: 4 waves per SIMD) and any Lmax works.  The q.k
+// partial is reduced over the key's 8 lanes (xor 1, 2, 4), the softmax statistics and the P.V
+// partials over the 8 key groups (xor 8, 16, 32).  The per-slot inputs (rowmap, compact position)
+// are loaded together with the qkv row: one dependent round trip before the K/V loads.  The new
+// token's k/v (position pos[r]) comes from the qkv row in registers and is written to the cache
+// for later steps.  HBM-bound on the K/V bytes: 2 * (pos+1) * 64 * 2 B per (row, head).
+// DPP: the in-group dot product reduction (common.h's sum8) and the first step of the cross-group
+// max (row_mirror, i <-> 15 - i: valid once the value is uniform within 8-lane groups) by DPP
+// instead of ds_bpermute.
 
-// decode_attn6: decode_attn5's wave-per-(row, head) layout with the keys taken in phases of 64
-// (8 key groups x 8 keys, one 1 KiB wave-load each for K and V) and an online softmax across
-// phases, so a wave holds 64 keys' K/V in registers instead of 128 (~100 VGPRs: 4 waves per
-// SIMD instead of 2) and any Lmax works.  The per-slot inputs (rowmap, compact position) are
-// loaded together with the qkv row: one dependent round trip before the K/V loads.  With one
-// phase (p < 64) the arithmetic equals decode_attn5's.
-// DPP lane exchanges for the reductions inside a wave (VALU, no LDS round trip):
-// xor 1 / xor 2 = quad_perm [1,0,3,2] / [2,3,0,1]; the other quad of an 8-lane group via
-// row_half_mirror (lane i <-> 7 - i), valid once the value is uniform within each quad; the other
-// 8-lane group of a 16-lane row via row_mirror (i <-> 15 - i), valid once uniform within groups
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// sum over the 8 lanes of a group: the same additions, in the same order, as
-// s += shfl_xor(s, 1); s += shfl_xor(s, 2); s += shfl_xor(s, 4)  (bitwise equal results)
-__device__ __forceinline__ float group8_sum_dpp(float s) {
-  s += dpp_f<0xB1>(s);
-  s += dpp_f<0x4E>(s);
-  return s + dpp_f<0x141>(s);
-}
-
-// PF: the next phase's K/V loads are issued before the current phase's math (two phases in
-// flight per wave; the wait lands after the math instead of before it).  DPP: the in-group dot
-// product reduction and the first step of the cross-group max by DPP instead of ds_bpermute.
 // 8 bf16 in a uint4 <-> 8 floats by bit operations (element t in the low / high half of word
 // t / 2): no type-punned pointer into a register array, which kept such arrays in scratch memory
 __device__ __forceinline__ void bf8_unpack(const uint4& u, float (&f)[8]) {
@@ -692,13 +583,13 @@ template <> struct Pk8<float> {
 // merged through LDS at the end: SPLIT times the waves for the bs=64 decode's 768 (row, head)
 // pairs, each with a shorter chain of phases (requires heads % (4 / SPLIT) == 0, rows without
 // rowmap; no early exit before the barrier).
-template <typename T, int KPP = 64, bool PF = false, bool DPP = false, int SPLIT = 1>
+template <typename T, int KPP, bool DPP, int SPLIT>
 __global__ __launch_bounds__(256) void decode_attn6_kernel(
     const T* __restrict__ qkv, int D, int heads, T* __restrict__ kc, T* __restrict__ vc, int Lmax,
     const int* __restrict__ pos, const int* __restrict__ kvrow, T* __restrict__ out,
     const int* __restrict__ rowmap, const int* __restrict__ cpos, int nphys, int rgrp) {
   using V8 = Pk8<T>;
-  static_assert(SPLIT == 1 || ((SPLIT == 2 || SPLIT == 4) && !PF), "SPLIT 2 / 4 without prefetch");
+  static_assert(SPLIT == 1 || SPLIT == 2 || SPLIT == 4, "SPLIT 1, 2 or 4");
   constexpr int HD = 64, EPC = 8, NG = KPP / 8;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int slice = wid % SPLIT;
@@ -723,7 +614,7 @@ __global__ __launch_bounds__(256) void decode_attn6_kernel(
     if (grp == 0) V8::zero().st(out + (long)c * D + h * HD + sub * EPC);
     return;
   }
-  // wave-uniform (one (row, head) per wave): scalar branches for the phase loop and prefetch
+  // wave-uniform (one (row, head) per wave): scalar branches for the phase loop
   const int p = __builtin_amdgcn_readfirstlane(min(cpos ? p0 : pos[r], Lmax - 1));
   const long rh = ((long)r * heads + h) * Lmax;
   // the new token's K/V are stored at the END: the phases never read slot p (they take the new
@@ -740,33 +631,28 @@ __global__ __launch_bounds__(256) void decode_attn6_kernel(
   // min(j, p - 1), or slot 0 at p == 0) and the key is then chosen by value: cached for j < p,
   // the new token for j == p, zero past it.  (Loads under a divergent `if` were each waited
   // for inside their branch: one round trip per key group instead of one per phase.)
-  V8 kr[NG], vr[NG], kx[NG], vx[NG];
   // (beam: the kvrow source rows of the whole phase are loaded first, under one uniform branch)
-#define ZS_LOAD_PHASE(BASE, KA, VA)                                                            \
-  do {                                                                                         \
-    int jc[NG], srow[NG];                                                                      \
-    _Pragma("unroll") for (int i = 0; i < NG; ++i) {                                           \
-      jc[i] = max(min((BASE) + i * 8 + grp, p - 1), 0);                                        \
-      srow[i] = r;                                                                             \
-    }                                                                                          \
-    if (kvrow) {                                                                               \
-      _Pragma("unroll") for (int i = 0; i < NG; ++i) srow[i] = kvrow[(long)r * Lmax + jc[i]];  \
-    }                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < NG; ++i) {                                           \
-      const long src = ((long)srow[i] * heads + h) * Lmax + jc[i];                             \
-      KA[i] = V8::ld(kc + src * HD + sub * EPC);                                               \
-      VA[i] = V8::ld(vc + src * HD + sub * EPC);                                               \
-    }                                                                                          \
-  } while (0)
-  if (PF) ZS_LOAD_PHASE(0, kr, vr);
+  V8 kr[NG], vr[NG];
   for (int base = slice * KPP; base <= p; base += KPP * SPLIT) {
-    if (PF) {
-      if (base + KPP <= p) ZS_LOAD_PHASE(base + KPP, kx, vx);
-    } else {
-      ZS_LOAD_PHASE(base, kr, vr);
+    {
+      int jc[NG], srow[NG];
+#pragma unroll
+      for (int i = 0; i < NG; ++i) {
+        jc[i] = max(min(base + i * 8 + grp, p - 1), 0);
+        srow[i] = r;
+      }
+      if (kvrow) {
+#pragma unroll
+        for (int i = 0; i < NG; ++i) srow[i] = kvrow[(long)r * Lmax + jc[i]];
+      }
+#pragma unroll
+      for (int i = 0; i < NG; ++i) {
+        const long src = ((long)srow[i] * heads + h) * Lmax + jc[i];
+        kr[i] = V8::ld(kc + src * HD + sub * EPC);
+        vr[i] = V8::ld(vc + src * HD + sub * EPC);
+      }
     }
-    // the by-value key choice, applied where the phase is consumed (a prefetched phase is not
-    // waited for early)
+    // the by-value key choice
 #pragma unroll
     for (int i = 0; i < NG; ++i) {
       const int j = base + i * 8 + grp;
@@ -784,7 +670,7 @@ __global__ __launch_bounds__(256) void decode_attn6_kernel(
 #pragma unroll
       for (int t = 0; t < EPC; ++t) sv += q[t] * kf[t];
       if (DPP) {
-        sv = group8_sum_dpp(sv);
+        sv = sum8(sv);
       } else {
         sv += __shfl_xor(sv, 1, 64);
         sv += __shfl_xor(sv, 2, 64);
@@ -811,12 +697,7 @@ __global__ __launch_bounds__(256) void decode_attn6_kernel(
 #pragma unroll
       for (int t = 0; t < EPC; ++t) o[t] += e * vf[t];
     }
-    if (PF) {
-#pragma unroll
-      for (int i = 0; i < NG; ++i) { kr[i] = kx[i]; vr[i] = vx[i]; }
-    }
   }
-#undef ZS_LOAD_PHASE
 #pragma unroll
   for (int d = 8; d < 64; d <<= 1) {
     sum += __shfl_xor(sum, d, 64);
@@ -983,6 +864,66 @@ __global__ __launch_bounds__(64) void cross_attn_kernel(const T* __restrict__ q,
   for (int t = 0; t < 4; ++t) if (lane + 64 * t < hd) stf(orow + lane + 64 * t, o[t]);
 }
 
+// ------------------------------------------------------------------ decode attention dispatch
+// Which decode_attn6_kernel instantiation a decode attention call runs: keys per phase, DPP or
+// ds_bpermute reductions, waves per (row, head).  kpp == 0: no plan (f32 outside the two-wave
+// small-R case: zs_decode_attention's fallback kernels).
+struct DecodePlan {
+  int kpp;
+  bool dpp;
+  int split;
+};
+
+// Direct calls up to small_rmax rows (few waves: nothing hides a phase's round trip) take long
+// phases and split a (row, head)'s keys over waves as attn_split says; every other call, and every
+// rowmap call (is_map: compaction runs at >= 512 rows), takes the decode_attn5 knob's phase length
+// with one wave per (row, head).  zs_decode_attention and zs_decode_attention_map both ask here, so
+// a compacted decode step runs the kernel its uncompacted step runs.
+static DecodePlan decode_plan(int dtype, int R, int heads, bool is_map) {
+  const bool bf = dtype == ZS_BF16;
+  if (!is_map && R <= g_small_rmax && g_small_attn) {
+    if (bf && g_attn_split == 4) return {32, true, 4};
+    if (g_attn_split && heads % 2 == 0) return {bf && g_attn_split != 3 ? 64 : 32, true, 2};
+    return bf ? DecodePlan{128, true, 1} : DecodePlan{0, false, 0};
+  }
+  if (!bf) return {0, false, 0};
+  switch (g_decode_attn5) {      // zs_tune_set admits 6, 4, 3 and 2
+    case 6: return {16, true, 1};
+    case 4: return {16, false, 1};
+    case 3: return {32, false, 1};
+    default: return {64, false, 1};
+  }
+}
+
+// the one launch site of decode_attn6_kernel: the closed list of its instantiations
+static int decode_attn6_launch(const DecodePlan& pl, int dtype, const void* qkv, int R, int D,
+                               int heads, void* kc, void* vc, int Lmax, const int* pos,
+                               const int* kvrow, void* out, const int* rowmap, const int* cpos,
+                               int nphys, int rgrp, hipStream_t st) {
+  const dim3 grid(R, cdiv(heads, 4 / pl.split));
+#define DA6(T, KPP, DPP, SPLIT)                                                                  \
+  if (dtype == (sizeof(T) == 2 ? ZS_BF16 : ZS_F32) && pl.kpp == KPP && pl.dpp == DPP &&          \
+      pl.split == SPLIT) {                                                                       \
+    hipLaunchKernelGGL((decode_attn6_kernel<T, KPP, DPP, SPLIT>), grid, dim3(256), 0, st,        \
+                       (const T*)qkv, D, heads, (T*)kc, (T*)vc, Lmax, pos, kvrow, (T*)out,       \
+                       rowmap, cpos, nphys, rgrp);                                               \
+    ZS_LAUNCH_CHECK();                                                                           \
+    return 0;                                                                                    \
+  }
+  DA6(bf16_t, 32, true, 4)
+  DA6(bf16_t, 32, true, 2)
+  DA6(bf16_t, 64, true, 2)
+  DA6(bf16_t, 128, true, 1)
+  DA6(float, 32, true, 2)
+  DA6(bf16_t, 16, true, 1)
+  DA6(bf16_t, 16, false, 1)
+  DA6(bf16_t, 32, false, 1)
+  DA6(bf16_t, 64, false, 1)
+#undef DA6
+  return fail(ZS_ERR_UNSUPPORTED, "decode attention: no kernel for dtype %d, %d-key phases, split %d",
+              dtype, pl.kpp, pl.split);
+}
+
 }  // namespace zs
 
 using namespace zs;
@@ -1081,36 +1022,8 @@ extern "C" int zs_decode_attention_map(const void* qkv, int R, const int* rowmap
              "zs_decode_attention_map: head_dim must be 64");
   ZS_REQUIRE(dtype == ZS_BF16 && Lmax > 0 && Lmax <= 4096,
              "zs_decode_attention_map: bf16 only, Lmax <= 4096");
-  // the same kernel (and phase length) as zs_decode_attention picks for this knob setting, so a
-  // compacted decode computes exactly what the uncompacted one does
-  if (g_decode_attn5 == 1 && cpos == nullptr && Lmax <= 8 * DA5_MAXI) {
-    hipLaunchKernelGGL(decode_attn5_kernel<bf16_t>, dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, (const int*)nullptr, (bf16_t*)out, rowmap, nphys);
-  } else if (g_decode_attn5 == 2) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 64>), dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, (const int*)nullptr, (bf16_t*)out, rowmap, cpos, nphys, 1);
-  } else if (g_decode_attn5 == 4) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 16>), dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, (const int*)nullptr, (bf16_t*)out, rowmap, cpos, nphys, 1);
-  } else if (g_decode_attn5 == 5) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 16, true>), dim3(R, cdiv(heads, 4)), dim3(256),
-                       0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, (const int*)nullptr, (bf16_t*)out, rowmap, cpos, nphys, 1);
-  } else if (g_decode_attn5 == 6) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 16, false, true>), dim3(R, cdiv(heads, 4)),
-                       dim3(256), 0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc,
-                       (bf16_t*)vc, Lmax, pos, (const int*)nullptr, (bf16_t*)out, rowmap, cpos,
-                       nphys, 1);
-  } else {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 32>), dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, (const int*)nullptr, (bf16_t*)out, rowmap, cpos, nphys, 1);
-  }
-  ZS_LAUNCH_CHECK();
-  return 0;
+  return decode_attn6_launch(decode_plan(dtype, R, heads, true), dtype, qkv, R, D, heads, kc, vc,
+                             Lmax, pos, nullptr, out, rowmap, cpos, nphys, 1, S(stream));
 }
 
 extern "C" int zs_cross_attention(const void* q, int ldq, const void* k, const void* v, int ldkv,
@@ -1136,118 +1049,26 @@ extern "C" int zs_decode_attention(const void* qkv, int R, int D, int heads, voi
   ZS_REQUIRE(R > 0 && heads > 0 && D / heads == 64 && D % heads == 0,
              "zs_decode_attention: head_dim must be 64");
   ZS_REQUIRE(Lmax > 0 && Lmax <= 4096, "zs_decode_attention: Lmax");
-  dim3 grid(R, heads);
-  // beam rows (kvrow != NULL): groups of g_beam_xcd consecutive rows per XCD (decode_attn6_kernel)
-  const int rg = (kvrow && g_beam_xcd > 1 && R % (8 * g_beam_xcd) == 0) ? g_beam_xcd : 1;
-  if (dtype == ZS_F32 && R <= g_small_rmax && g_small_attn && g_attn_split && heads % 2 == 0) {
-    // the f32 parity mode's decode: the bf16 path's two-wave split with 32-key phases
-    hipLaunchKernelGGL((decode_attn6_kernel<float, 32, false, true, 2>), dim3(R, heads / 2),
-                       dim3(256), 0, S(stream), (const float*)qkv, D, heads, (float*)kc,
-                       (float*)vc, Lmax, pos, kvrow, (float*)out, (const int*)nullptr,
-                       (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
+  const DecodePlan pl = decode_plan(dtype, R, heads, false);
+  if (pl.kpp) {
+    // beam rows (kvrow != NULL): groups of g_beam_xcd consecutive rows per XCD
+    const int rg = (kvrow && g_beam_xcd > 1 && R % (8 * g_beam_xcd) == 0) ? g_beam_xcd : 1;
+    return decode_attn6_launch(pl, dtype, qkv, R, D, heads, kc, vc, Lmax, pos, kvrow, out, nullptr,
+                               nullptr, R, rg, S(stream));
   }
-  if (dtype == ZS_BF16 && R <= g_small_rmax && g_small_attn && g_attn_split == 4) {
-    // each (row, head)'s keys over four waves, 32-key phases (one phase per wave at L <= 128)
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 32, false, true, 4>), dim3(R, heads),
-                       dim3(256), 0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc,
-                       (bf16_t*)vc, Lmax, pos, kvrow, (bf16_t*)out, (const int*)nullptr,
-                       (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && R <= g_small_rmax && g_small_attn && g_attn_split && heads % 2 == 0) {
-    // few waves (R x heads): each (row, head)'s keys over two waves, KPP-key phases (64: all
-    // keys of L <= 128 in flight at once, half per wave; 32 (attn_split 3): two phases a wave)
-    if (g_attn_split == 3)
-      hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 32, false, true, 2>), dim3(R, heads / 2),
-                         dim3(256), 0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc,
-                         (bf16_t*)vc, Lmax, pos, kvrow, (bf16_t*)out, (const int*)nullptr,
-                         (const int*)nullptr, R, rg);
-    else
-      hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 64, false, true, 2>), dim3(R, heads / 2),
-                         dim3(256), 0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc,
-                         (bf16_t*)vc, Lmax, pos, kvrow, (bf16_t*)out, (const int*)nullptr,
-                         (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && R <= g_small_rmax && g_small_attn) {
-    // few waves (R x heads): nothing hides a phase's round trip, so take 128-key phases: every
-    // key of a row in flight at once, one HBM round trip at L <= 128
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 128, false, true>), dim3(R, cdiv(heads, 4)),
-                       dim3(256), 0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc,
-                       (bf16_t*)vc, Lmax, pos, kvrow, (bf16_t*)out, (const int*)nullptr,
-                       (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && g_decode_attn5 == 4) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 16>), dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, kvrow, (bf16_t*)out, (const int*)nullptr, (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && g_decode_attn5 == 6) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 16, false, true>), dim3(R, cdiv(heads, 4)),
-                       dim3(256), 0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc,
-                       (bf16_t*)vc, Lmax, pos, kvrow, (bf16_t*)out, (const int*)nullptr,
-                       (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && g_decode_attn5 == 5) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 16, true>), dim3(R, cdiv(heads, 4)), dim3(256),
-                       0, S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, kvrow, (bf16_t*)out, (const int*)nullptr, (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && g_decode_attn5 == 3) {
-    hipLaunchKernelGGL((decode_attn6_kernel<bf16_t, 32>), dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, kvrow, (bf16_t*)out, (const int*)nullptr, (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && g_decode_attn5 == 2) {
-    hipLaunchKernelGGL(decode_attn6_kernel<bf16_t>, dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, kvrow, (bf16_t*)out, (const int*)nullptr, (const int*)nullptr, R, rg);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  if (dtype == ZS_BF16 && Lmax <= 8 * DA5_MAXI && g_decode_attn5) {
-    hipLaunchKernelGGL(decode_attn5_kernel<bf16_t>, dim3(R, cdiv(heads, 4)), dim3(256), 0,
-                       S(stream), (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax,
-                       pos, kvrow, (bf16_t*)out, (const int*)nullptr, R);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
+  // f32 without a plan: the LDS-staged kernel while a row's keys fit, else scores in LDS only
+  const dim3 grid(R, heads);
   if (Lmax <= 512) {
     const size_t smem = (400 + 66 * (size_t)Lmax) * sizeof(float);
-    if (dtype == ZS_BF16)
-      hipLaunchKernelGGL(decode_attn4_kernel<bf16_t>, grid, dim3(256), smem, S(stream),
-                         (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax, pos, kvrow,
-                         (bf16_t*)out);
-    else
-      hipLaunchKernelGGL(decode_attn4_kernel<float>, grid, dim3(256), smem, S(stream),
-                         (const float*)qkv, D, heads, (float*)kc, (float*)vc, Lmax, pos, kvrow,
-                         (float*)out);
-    ZS_LAUNCH_CHECK();
-    return 0;
-  }
-  const size_t smem = (128 + (size_t)Lmax) * sizeof(float);
-  if (dtype == ZS_BF16)
-    hipLaunchKernelGGL(decode_attn_kernel<bf16_t>, grid, dim3(64), smem, S(stream),
-                       (const bf16_t*)qkv, D, heads, (bf16_t*)kc, (bf16_t*)vc, Lmax, pos, kvrow,
-                       (bf16_t*)out);
-  else
+    hipLaunchKernelGGL(decode_attn4_kernel<float>, grid, dim3(256), smem, S(stream),
+                       (const float*)qkv, D, heads, (float*)kc, (float*)vc, Lmax, pos, kvrow,
+                       (float*)out);
+  } else {
+    const size_t smem = (128 + (size_t)Lmax) * sizeof(float);
     hipLaunchKernelGGL(decode_attn_kernel<float>, grid, dim3(64), smem, S(stream),
                        (const float*)qkv, D, heads, (float*)kc, (float*)vc, Lmax, pos, kvrow,
                        (float*)out);
+  }
   ZS_LAUNCH_CHECK();
   return 0;
 }

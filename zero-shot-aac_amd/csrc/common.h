@@ -81,6 +81,42 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Lane exchanges without an LDS round trip (no ds_bpermute): DPP inside a row of 16 lanes,
+// v_permlane16/32_swap across rows.  CTRL: 0xB1 / 0x4E = quad_perm [1,0,3,2] / [2,3,0,1] (lane ^ 1,
+// lane ^ 2), 0x141 = row_half_mirror (lane i <-> 7 - i of an 8-lane group), 0x140 = row_mirror
+// (i <-> 15 - i), 0x128 = row_ror:8 (lane ^ 8).
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+// The sum over the 8 lanes of a group (lane & 7), on each of them.  Bitwise equal to
+// s += shfl_xor(s, 1); s += shfl_xor(s, 2); s += shfl_xor(s, 4): the first two steps read the same
+// partner lanes, and after them s is uniform within each quad, so the mirrored lane 7 - i holds
+// what lane i ^ 4 holds and the third addition has the same two operands.
+__device__ __forceinline__ float sum8(float s) {
+  s += dpp_f<0xB1>(s);
+  s += dpp_f<0x4E>(s);
+  return s + dpp_f<0x141>(s);
+}
+__device__ __forceinline__ float xor8(float v) { return dpp_f<0x128>(v); }   // lane ^ 8's v
+// v combined with the partner lane's v (lane ^ 16 / lane ^ 32), the same value on both lanes
+__device__ __forceinline__ float add16(float v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float add32(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float max16(float v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float max32(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
 // block-wide sum through LDS (blockDim multiple of 64, <= 1024)
 __device__ __forceinline__ float block_sum(float v, float* red) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;

@@ -225,33 +225,7 @@ __device__ __forceinline__ int otid() {
   asm volatile("" : "+v"(t));
   return t;
 }
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sum8(float s) {     // over the 8 lanes of each 8-lane group
-  s += dppf<0xB1>(s);
-  s += dppf<0x4E>(s);
-  return s + dppf<0x141>(s);
-}
-__device__ __forceinline__ float xor8(float v) { return dppf<0x128>(v); }   // row_ror:8
-// v + the partner lane's v (lane ^ 16 / lane ^ 32), the same value on both lanes
-__device__ __forceinline__ float add16(float v) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float add32(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float max16(float v) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float max32(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
+// (sum8, xor8, add16 / add32, max16 / max32: the lane exchanges of common.h)
 // workgroup barrier for LDS hand-offs; waits for nothing in flight in vector memory
 __device__ __forceinline__ void lds_sync() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -295,7 +295,15 @@ extern "C" int zs_tune_set(const char* key, int value) {
   if (!strcmp(key, "skinny_mode")) { g_skinny_mode = value; return 0; }
   if (!strcmp(key, "gemm_fast")) { g_gemm_fast = value; return 0; }
   if (!strcmp(key, "f32_fast")) { g_f32_fast = value; return 0; }
-  if (!strcmp(key, "decode_attn5")) { g_decode_attn5 = value; return 0; }
+  if (!strcmp(key, "decode_attn5")) {
+    if (value == 0 || value == 1 || value == 5)
+      return fail(ZS_ERR_ARG, "zs_tune_set: decode_attn5 = %d chose a kernel that is retired "
+                  "(6, 4, 3 or 2: decode_attn6's phase length and reductions)", value);
+    ZS_REQUIRE(value == 2 || value == 3 || value == 4 || value == 6,
+               "zs_tune_set: decode_attn5 = %d (6, 4, 3 or 2)", value);
+    g_decode_attn5 = value;
+    return 0;
+  }
   if (!strcmp(key, "window_mfma")) { g_window_mfma = value; return 0; }
   if (!strcmp(key, "fast_ns")) { g_fast_ns = value; return 0; }
   if (!strcmp(key, "fast_tile")) { g_fast_tile = value; return 0; }

@@ -27,22 +27,11 @@ namespace zs {
 // clips over 40 rounds, tools/prompt_stress.py grid mode; none alone or beside GEMMs; the cause
 // in that kernel was not isolated, this one shares nothing with it.)
 constexpr int PK_MAX = 16;          // k <= 16
-template <int CTRL>
-__device__ __forceinline__ float pdpp(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// the sum of v over the 64 lanes, on every lane, in one fixed order
+// the sum of v over the 64 lanes, on every lane, in one fixed order: 8-lane sums, then lane ^ 8,
+// lane ^ 16 and lane ^ 32
 __device__ __forceinline__ float wave_sum_dpp(float v) {
-  v += pdpp<0xB1>(v);                              // quad_perm [1,0,3,2]
-  v += pdpp<0x4E>(v);                              // quad_perm [2,3,0,1]
-  v += pdpp<0x141>(v);                             // row_half_mirror: 8-lane sums
-  v += pdpp<0x128>(v);                             // row_ror:8: 16-lane sums
-  {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  v = sum8(v);
+  return add32(add16(v + xor8(v)));
 }
 // top-k labels of clip blockIdx.x into sel[0..k) (uniform across the wave); K = k (3, the
 // reference's sound_effect_num) or PK_MAX (any k <= 16)

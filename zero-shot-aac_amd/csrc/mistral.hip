@@ -670,34 +670,13 @@ __global__ __launch_bounds__(256) void mistral_silu_mul_kernel(const float* __re
   st4(act + idx, o[0], o[1], o[2], o[3]);
 }
 
-// in-wave reductions of the attention kernels without LDS round trips (DPP within rows of 16,
-// v_permlane16/32_swap across them), the same butterfly order as __shfl_xor 1, 2, 4 / 8, 16, 32
-template <int CTRL>
-__device__ __forceinline__ float m_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float m_sum8(float s) {          // over lane & 7
-  s += m_dpp<0xB1>(s);                                        // quad_perm [1,0,3,2]
-  s += m_dpp<0x4E>(s);                                        // quad_perm [2,3,0,1]
-  return s + m_dpp<0x141>(s);                                 // row_half_mirror
-}
-__device__ __forceinline__ float m_pair16(float v) {        // v + lane ^ 16's v
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float m_pair32(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
+// in-wave reductions of the attention kernels from common.h's lane primitives, the same
+// butterfly order as __shfl_xor 1, 2, 4 (sum8) / 8, 16, 32 (below)
 __device__ __forceinline__ float m_max_grp(float v) {       // over lane >> 3
-  v = fmaxf(v, m_dpp<0x128>(v));                              // row_ror:8 = lane ^ 8
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  return max32(max16(fmaxf(v, xor8(v))));
 }
 __device__ __forceinline__ float m_add_grp(float v) {
-  return m_pair32(m_pair16(v + m_dpp<0x128>(v)));
+  return add32(add16(v + xor8(v)));
 }
 
 // causal GQA attention, one wave per (query row m, q head h): keys 0..pos[m] of the sequence
@@ -744,7 +723,7 @@ __global__ __launch_bounds__(256) void mistral_attn_kernel(const T* __restrict__
       float sv = 0.f;
 #pragma unroll
       for (int d = 0; d < DPL; ++d) sv += qv[d] * kf[u][d];
-      sv = m_sum8(sv);
+      sv = sum8(sv);
       sv = (j0 + 8 * u + grp <= p) ? sv * scale : -INFINITY;
       float pm = m_max_grp(sv);
       const float mn = fmaxf(mx, pm);
@@ -865,7 +844,7 @@ __global__ __launch_bounds__(256) void mistral_decode_attn_kernel(
       float sv = 0.f;
 #pragma unroll
       for (int d = 0; d < DPL; ++d) sv += qv[d] * kf[u][d];
-      sv = m_sum8(sv);
+      sv = sum8(sv);
       update((j0 + 8 * u + grp < p) ? sv * scale : -INFINITY, vf[u]);
     }
   }
@@ -873,7 +852,7 @@ __global__ __launch_bounds__(256) void mistral_decode_attn_kernel(
     float sv = 0.f;
 #pragma unroll
     for (int d = 0; d < DPL; ++d) sv += qv[d] * kn[d];
-    sv = m_sum8(sv);
+    sv = sum8(sv);
     update(grp == 0 ? sv * scale : -INFINITY, vn);
   }
   l = m_add_grp(l);

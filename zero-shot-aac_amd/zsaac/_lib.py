@@ -153,7 +153,7 @@ def lib():
             for kv in filter(None, os.environ.get("ZSAAC_TUNE", "").split(",")):
                 k, v = kv.split("=")
                 if h.zs_tune_set(k.strip().encode(), int(v)) != 0:
-                    raise ZsError(f"ZSAAC_TUNE: unknown knob {k!r}")
+                    raise ZsError(f"ZSAAC_TUNE: unknown knob or refused value {kv!r}")
             _lib = h
     return _lib
 

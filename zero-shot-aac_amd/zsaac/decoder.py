@@ -354,8 +354,9 @@ class Gpt2Decoder:
         self.all_done = torch.zeros(3, **i32)
         # greedy row compaction: decode only the rows that have not stopped, in buckets of
         # `bucket` rows (>= `min_bucket`, so the GEMMs stay in the tiled regime); bf16 only
-        # (decode_attn5), and the per-row arithmetic of every kernel is independent of the row
-        # count, so the ids equal the uncompacted decode's.
+        # (zs_decode_attention_map), and the per-row arithmetic of every kernel is independent of
+        # the row count -- the rowmap decode attention runs the decode_attn6_kernel instantiation
+        # the direct call runs at these row counts -- so the ids equal the uncompacted decode's.
         self.bucket, self.min_bucket = 256, 512
         if compact is None:
             compact = dt == torch.bfloat16
