@@ -736,7 +736,14 @@ int zs_gpt2_decode_persist(int R, int Lmax, int max_steps, int stop0, int stop1,
 /* zs_gpt2_decode_phases: `steps` decode steps of the same computation as separate launches (one
  * per phase of every block, the LM head and the bookkeeping: 62 per step; each a no-op once
  * all_done[0] is set, so a graph-captured chunk can run past the end) -- the per-step path of
- * zs_gpt2_decode_persist (no co-residency needed; the give-up fallback), bit-identical to it. */
+ * zs_gpt2_decode_persist (no co-residency needed; the give-up fallback), bit-identical to it.
+ * Launch i of a step: 5 l + {0 A, 1 B, 2 C, 3 D, 4 E} for block l, 60 = F (ln_f + LM head), 61 =
+ * the bookkeeping.  zs_tune_set("dg_win_lo", a) / ("dg_win_hi", b) (defaults 0 / 62, 0 <= a <= 61,
+ * 1 <= b <= 62) narrow a call, of this entry and of zs_gpt2_decode_phases_f32, to the launches
+ * a <= i < b: then steps must be 1, and an empty window (a >= b) fails with ZS_ERR_ARG.  Every call
+ * still zeroes the workspace's first 4096 bytes (barrier words and the argmax keys F raises), and
+ * every phase hands its output on through memory, so a test can run one phase on inputs it wrote
+ * (tests/test_gpu_grid_kernels.py); C and E update x in place: once per workspace contents. */
 int zs_gpt2_decode_phases(int R, int Lmax, int max_steps, int stop0, int stop1, int V,
                           const void* wte, const void* wpe, const void* wte_packed,
                           float temperature, const void* const* layer_w,

@@ -84,6 +84,55 @@ def test_tune_set_decode_attn5_admits_only_live_values(libpath):
         _lib.call("zs_tune_set", b"decode_attn5", 6)
 
 
+def test_tune_set_phase_launch_window_bounds(libpath):
+    """dg_win_lo / dg_win_hi narrow the grid decode's phase launches to the launches [lo, hi) of a
+    step's 62: lo in 0 .. 61, hi in 1 .. 62, anything else fails with ZS_ERR_ARG and a message
+    naming the value, and leaves the knob where it was (0 / 62 at the end).  An empty window and
+    a narrowed one with steps != 1 are refused by the phase entry points themselves, after their
+    argument checks and before any launch (tests/test_gpu_grid_kernels.py, which has the device
+    buffers those checks want)."""
+    from zsaac import _lib, ops
+    lib = _lib.lib()
+    assert ops.DECODE_PHASE_LAUNCHES == 62
+    try:
+        for k, bad in ((b"dg_win_lo", (-1, 62, 1000)), (b"dg_win_hi", (0, -3, 63))):
+            for v in bad:
+                with pytest.raises(_lib.ZsError, match=rf"{k.decode()} = {v}\b"):
+                    _lib.call("zs_tune_set", k, v)
+                assert lib.zs_tune_set(k, v) == -1                    # ZS_ERR_ARG
+        for lo, hi in ((0, 1), (61, 62), (17, 18), (60, 62), (0, 62)):
+            assert _lib.call("zs_tune_set", b"dg_win_lo", lo) == 0
+            assert _lib.call("zs_tune_set", b"dg_win_hi", hi) == 0
+    finally:
+        _lib.call("zs_tune_set", b"dg_win_lo", 0)
+        _lib.call("zs_tune_set", b"dg_win_hi", 62)
+
+
+def test_phase_window_wrapper_restores_the_default(libpath, monkeypatch):
+    """ops.gpt2_decode_phase_window sets the window, runs one step's launches and restores 0 / 62
+    in a finally -- also when the launch raises -- so a later call or captured graph never sees a
+    narrowed window.  Out-of-range and empty windows are refused before any knob moves."""
+    from zsaac import ops
+    from zsaac._lib import ZsError
+    seen = []
+    monkeypatch.setattr(ops, "call", lambda name, *a: seen.append((name,) + a) or 0)
+
+    def boom(*a, **kw):
+        seen.append(("run", kw))
+        raise ZsError("launch failed")
+    monkeypatch.setattr(ops, "gpt2_decode_phases", boom)
+    with pytest.raises(ZsError, match="launch failed"):
+        ops.gpt2_decode_phase_window(first=7, last=8, grid=48)
+    assert seen == [("zs_tune_set", b"dg_win_lo", 7), ("zs_tune_set", b"dg_win_hi", 8),
+                    ("run", {"steps": 1, "grid": 48}),
+                    ("zs_tune_set", b"dg_win_lo", 0), ("zs_tune_set", b"dg_win_hi", 62)]
+    for first, last in ((5, 5), (9, 3), (-1, 4), (0, 63)):
+        del seen[:]
+        with pytest.raises(ZsError, match="window"):
+            ops.gpt2_decode_phase_window(first=first, last=last)
+        assert seen == []
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from zsaac import ops

@@ -12,6 +12,10 @@ per-step path and the give-up fallback) run one canonical arithmetic, so
   * a give-up (forced at the first barrier, or in the middle of the launch at a chosen step)
     resumes from the last committed step on the phase launches with ids equal to an
     uninterrupted run's, synchronously and under ConcurrentRunner.
+
+Everything here looks at argmax ids and integer state.  The VALUES of every phase -- q, K / V,
+att, x / xb, hid, the logit behind each id -- are pinned against float64 references, one phase
+launch at a time, in tests/test_gpu_grid_kernels.py (references: tests/grid_ref.py).
 """
 import os
 import sys

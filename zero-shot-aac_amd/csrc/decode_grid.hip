@@ -68,6 +68,12 @@ int g_dg_exp = 0;    // zs_tune_set("dg_exp", m): traffic experiments (grid_benc
 int g_dg_dynf = 1;   // zs_tune_set("dg_dynf", 0): phase F all static in persistent launches too (A/B)
 int g_dp_abort = -1; // zs_tune_set("dp_abort_step", k): every workgroup gives up at the start of
                      // decode step k (a mid-launch give-up for the resume test); -1 = never
+// zs_tune_set("dg_win_lo", a) / ("dg_win_hi", b): the phase launches enqueue only the launches
+// a <= i < b of a step's 62 (A .. E of block l: 5 l + phase; F: 60; bookkeeping: 61); the default
+// 0 / 62 is the whole step.  A narrower window runs one step per call (tests/test_gpu_grid_kernels.py
+// checks each phase alone on inputs it wrote to the workspace); host code only
+int g_dg_win_lo = 0;
+int g_dg_win_hi = 62;
 namespace dg {
 
 constexpr int D = 768, NH = 12, HD = 64, DFF = 3072, NLY = 12, RM = 64, QKVN = 3 * D;
@@ -1922,20 +1928,33 @@ extern "C" int zs_gpt2_decode_persist(int R, int Lmax, int max_steps, int stop0,
 }
 
 namespace {
+constexpr int DG_LAUNCHES = 5 * dg::NLY + 2;   // per step: A .. E of every block, F, bookkeeping
+// the launch window of this call (zs_tune_set dg_win_lo / dg_win_hi): the whole step, or one step's
+// launches lo <= i < hi
+int dg_window(const char* who, int steps, int& lo, int& hi) {
+  lo = g_dg_win_lo;
+  hi = g_dg_win_hi;
+  ZS_REQUIRE(lo >= 0 && lo < hi && hi <= DG_LAUNCHES,
+             "%s: launch window [%d, %d) is empty or outside [0, %d)", who, lo, hi, DG_LAUNCHES);
+  ZS_REQUIRE((lo == 0 && hi == DG_LAUNCHES) || steps == 1,
+             "%s: a narrowed launch window [%d, %d) runs one step per call (steps %d)", who, lo, hi, steps);
+  return 0;
+}
 template <int G>
-int dg_phase_step(dg::Args& a, hipStream_t st) {
+int dg_phase_step(dg::Args& a, hipStream_t st, int lo, int hi) {
   using namespace dg;
+  const auto in = [&](int i) { return lo <= i && i < hi; };
   for (int l = 0; l < NLY; ++l) {
     a.layer = l;
-    hipLaunchKernelGGL((dg_phase_kernel<G, PH_A>), dim3(G), dim3(NT), 0, st, a);
-    hipLaunchKernelGGL((dg_phase_kernel<G, PH_B>), dim3(G), dim3(NT), 0, st, a);
-    hipLaunchKernelGGL((dg_phase_kernel<G, PH_C>), dim3(G), dim3(NT), 0, st, a);
-    hipLaunchKernelGGL((dg_phase_kernel<G, PH_D>), dim3(G), dim3(NT), 0, st, a);
-    hipLaunchKernelGGL((dg_phase_kernel<G, PH_E>), dim3(G), dim3(NT), 0, st, a);
+    if (in(5 * l + 0)) hipLaunchKernelGGL((dg_phase_kernel<G, PH_A>), dim3(G), dim3(NT), 0, st, a);
+    if (in(5 * l + 1)) hipLaunchKernelGGL((dg_phase_kernel<G, PH_B>), dim3(G), dim3(NT), 0, st, a);
+    if (in(5 * l + 2)) hipLaunchKernelGGL((dg_phase_kernel<G, PH_C>), dim3(G), dim3(NT), 0, st, a);
+    if (in(5 * l + 3)) hipLaunchKernelGGL((dg_phase_kernel<G, PH_D>), dim3(G), dim3(NT), 0, st, a);
+    if (in(5 * l + 4)) hipLaunchKernelGGL((dg_phase_kernel<G, PH_E>), dim3(G), dim3(NT), 0, st, a);
   }
   a.layer = 0;
-  hipLaunchKernelGGL((dg_phase_kernel<G, PH_F>), dim3(G), dim3(NT), 0, st, a);
-  hipLaunchKernelGGL(dg_book_kernel<Args>, dim3(1), dim3(64), 0, st, a);
+  if (in(5 * NLY)) hipLaunchKernelGGL((dg_phase_kernel<G, PH_F>), dim3(G), dim3(NT), 0, st, a);
+  if (in(5 * NLY + 1)) hipLaunchKernelGGL(dg_book_kernel<Args>, dim3(1), dim3(64), 0, st, a);
   ZS_LAUNCH_CHECK();
   return 0;
 }
@@ -1955,10 +1974,12 @@ extern "C" int zs_gpt2_decode_phases(int R, int Lmax, int max_steps, int stop0, 
                          all_done, ws, ws_bytes, grid);
   if (rc) return rc;
   ZS_REQUIRE(steps >= 1, "zs_gpt2_decode_phases: steps %d", steps);
+  int lo, hi;
+  if (const int wr = dg_window("zs_gpt2_decode_phases", steps, lo, hi)) return wr;
   ZS_CHECK_HIP(hipMemsetAsync(ws, 0, dg::WS_SYNC_BYTES, S(stream)));
   for (int s = 0; s < steps; ++s) {
-    const int r = grid == 48 ? dg_phase_step<48>(a, S(stream))
-                : grid == 96 ? dg_phase_step<96>(a, S(stream)) : dg_phase_step<192>(a, S(stream));
+    const int r = grid == 48 ? dg_phase_step<48>(a, S(stream), lo, hi)
+                : grid == 96 ? dg_phase_step<96>(a, S(stream), lo, hi) : dg_phase_step<192>(a, S(stream), lo, hi);
     if (r) return r;
   }
   return 0;
@@ -2090,20 +2111,23 @@ extern "C" int zs_gpt2_decode_phases_f32(int R, int Lmax, int max_steps, int sto
                            all_done, ws, ws_bytes, grid);
   if (rc) return rc;
   ZS_REQUIRE(steps >= 1, "zs_gpt2_decode_phases_f32: steps %d", steps);
+  int lo, hi;
+  if (const int wr = dg_window("zs_gpt2_decode_phases_f32", steps, lo, hi)) return wr;
+  const auto in = [&](int i) { return lo <= i && i < hi; };
   const hipStream_t st = S(stream);
   ZS_CHECK_HIP(hipMemsetAsync(ws, 0, WS_SYNC_BYTES, st));
   for (int s = 0; s < steps; ++s) {
     for (int l = 0; l < NLY; ++l) {
       a.layer = l;
-      hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_A>, dim3(f32::G), dim3(NT), 0, st, a);
-      hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_B>, dim3(f32::G), dim3(NT), 0, st, a);
-      hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_C>, dim3(f32::G), dim3(NT), 0, st, a);
-      hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_D>, dim3(f32::G), dim3(NT), 0, st, a);
-      hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_E>, dim3(f32::G), dim3(NT), 0, st, a);
+      if (in(5 * l + 0)) hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_A>, dim3(f32::G), dim3(NT), 0, st, a);
+      if (in(5 * l + 1)) hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_B>, dim3(f32::G), dim3(NT), 0, st, a);
+      if (in(5 * l + 2)) hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_C>, dim3(f32::G), dim3(NT), 0, st, a);
+      if (in(5 * l + 3)) hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_D>, dim3(f32::G), dim3(NT), 0, st, a);
+      if (in(5 * l + 4)) hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_E>, dim3(f32::G), dim3(NT), 0, st, a);
     }
     a.layer = 0;
-    hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_F>, dim3(f32::G), dim3(NT), 0, st, a);
-    hipLaunchKernelGGL(dg_book_kernel<f32::Args>, dim3(1), dim3(64), 0, st, a);
+    if (in(5 * NLY)) hipLaunchKernelGGL(f32::dg32_phase_kernel<PH_F>, dim3(f32::G), dim3(NT), 0, st, a);
+    if (in(5 * NLY + 1)) hipLaunchKernelGGL(dg_book_kernel<f32::Args>, dim3(1), dim3(64), 0, st, a);
     ZS_LAUNCH_CHECK();
   }
   return 0;

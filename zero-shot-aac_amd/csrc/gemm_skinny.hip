@@ -268,6 +268,8 @@ extern int g_dp_spin;       // decode_grid.hip
 extern int g_dp_abort;      // decode_grid.hip
 extern int g_dg_exp;
 extern int g_dg_dynf;       // decode_grid.hip
+extern int g_dg_win_lo;     // decode_grid.hip
+extern int g_dg_win_hi;     // decode_grid.hip
 extern int g_beam_xcd;      // attn.hip
 extern int g_f32_tile;      // gemm.hip
 
@@ -334,6 +336,18 @@ extern "C" int zs_tune_set(const char* key, int value) {
   if (!strcmp(key, "dp_abort_step")) { g_dp_abort = value; return 0; }
   if (!strcmp(key, "dg_exp")) { g_dg_exp = value; return 0; }
   if (!strcmp(key, "dg_dynf")) { g_dg_dynf = value; return 0; }
+  // the phase launches' window of a step's 62 launches [dg_win_lo, dg_win_hi); an empty one
+  // (lo >= hi) is refused by the phase entry points
+  if (!strcmp(key, "dg_win_lo")) {
+    ZS_REQUIRE(value >= 0 && value <= 61, "zs_tune_set: dg_win_lo = %d (0 .. 61)", value);
+    g_dg_win_lo = value;
+    return 0;
+  }
+  if (!strcmp(key, "dg_win_hi")) {
+    ZS_REQUIRE(value >= 1 && value <= 62, "zs_tune_set: dg_win_hi = %d (1 .. 62)", value);
+    g_dg_win_hi = value;
+    return 0;
+  }
   if (!strcmp(key, "beam_xcd")) { g_beam_xcd = value; return 0; }
   if (!strcmp(key, "f32_tile")) { g_f32_tile = value; return 0; }
   return fail(ZS_ERR_ARG, "zs_tune_set: unknown key %s", key);

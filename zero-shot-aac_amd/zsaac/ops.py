@@ -788,3 +788,22 @@ def gpt2_decode_phases_f32(*args, steps=1, grid=192):
     f32 launch)."""
     call("zs_gpt2_decode_phases_f32", *_decode_grid_args(*args, grid, f32=True), int(steps),
          int(grid), _s())
+
+
+DECODE_PHASE_LAUNCHES = 62      # per step: A .. E of each of the 12 blocks, F, the bookkeeping
+
+
+def gpt2_decode_phase_window(*args, first, last, grid=96, f32=False):
+    """Launches first <= i < last of ONE decode step's 62 phase launches (5 l + {A, B, C, D, E} of
+    block l, 60 = F, 61 = the bookkeeping) on the caller's state and workspace: the launch window
+    (zs_tune_set dg_win_lo / dg_win_hi) is narrowed for this call alone and restored whatever
+    happens, so no captured chunk graph ever sees it.  For the per-phase tests."""
+    _need(0 <= first < last <= DECODE_PHASE_LAUNCHES,
+          f"decode phase window [{first}, {last}) within [0, {DECODE_PHASE_LAUNCHES})")
+    try:
+        call("zs_tune_set", b"dg_win_lo", int(first))
+        call("zs_tune_set", b"dg_win_hi", int(last))
+        (gpt2_decode_phases_f32 if f32 else gpt2_decode_phases)(*args, steps=1, grid=grid)
+    finally:
+        call("zs_tune_set", b"dg_win_lo", 0)
+        call("zs_tune_set", b"dg_win_hi", DECODE_PHASE_LAUNCHES)
