@@ -223,6 +223,48 @@ int zs_patch_merge_ln(const float* x, int B, int H, int W, int C, const float* l
 int zs_ln_meanpool(const float* x, int B, int N, int C, const float* ln_w, const float* ln_b,
                    float* out, void* stream);
 
+/* ------------------------------------------------------------------ HTSAT tagging head
+ * htsat.py:830-894 (forward_features past the last stage): clip-level tags and frame-level sound
+ * events from the tokens zs_ln_meanpool reads.  Token n = f * 8 + t (frequency row f, time
+ * column t, an 8 x 8 map); the reference regroups it (834-839) into 32 time frames tau of 2
+ * frequency bins c:  tok(tau, c) = (2 (tau / 8) + c) * 8 + tau % 8.
+ *
+ * zs_tag_prep: htsat.py:830 (`norm`, eps 1e-5) and 834-847 up to `fine_grained_latent_output`
+ * before its x32 repeat, in one pass over x [B][64][C] f32:
+ *   xn [B][64][C] (dtype) = LayerNorm(x), the operand of zs_tag_conv;
+ *   fine [B][32][C] f32, fine[b][tau] = (xn[b][tok(tau, 0)] + xn[b][tok(tau, 1)]) / 2 taken from
+ *   the f32 xn before any rounding to bf16.
+ * Accepts B > 0 (B * 64 rows), C a multiple of 32 with C <= 2048, dtype ZS_F32 or ZS_BF16,
+ * non-NULL buffers; everything else is refused before any launch with the outputs untouched. */
+int zs_tag_prep(const float* x, int B, int C, const float* ln_w, const float* ln_b, void* xn,
+                int dtype, float* fine, void* stream);
+
+/* zs_tag_conv: htsat.py:849-894, `tscam_conv` = Conv2d(C, N, (2, 3), padding (0, 1)) over the
+ * (bin, frame) map, flatten, sigmoid, and the clip-level sigmoid of the time mean -- replacing the
+ * reference's reshape / permute / conv2d / interpolate sequence without an im2col matrix:
+ *   z[b][tau][k]   = bias[k] + sum_{c<2} sum_{d<3} sum_ch W[k][ch][c][d] xn[b][tok(tau+d-1, c)][ch]
+ *                    (terms with tau + d - 1 outside [0, 32) are zero)
+ *   frame[b][tau][k] = sigmoid(z)              [B][32][ldf] f32 (`framewise_output` before x32)
+ *   clip[b][k]       = sigmoid(mean_tau z)     [B][ldc] f32     (`clipwise_output`)
+ *   logits (may be NULL) = z, in frame's layout.
+ * Only columns [0, N) of a row are written.  xn [B][64][C] (dtype, from zs_tag_prep).  w_packed
+ * (dtype): the weight as a [Np][6 C] matrix, Np = N rounded up to 16 with zero rows past N,
+ * column (c * 3 + d) * C + ch = W[k][ch][c][d], in swin.hip's fragment packing
+ * [Np/16][6C/32][64][8]: frag(nt, ks)[lane][j] = W[16 nt + lane % 16][32 ks + 8 (lane / 16) + j].
+ * ZS_BF16: bf16 MFMA with f32 accumulation; ZS_F32: f32 MFMA (exact f32 products, summed 64
+ * at a time into a fresh accumulator that is then added to the total).  One
+ * workgroup per (clip, 128 classes): the time mean is tile-local, no atomics, every reduction in
+ * a fixed order -- a clip's outputs are bit-identical whatever B and whichever clips share the
+ * launch, and two equal weight rows give bit-equal columns.  With ldc a multiple of 8 and the
+ * padding of clip holding -inf, zs_sim_topk_finalize(clip, idx, B, ldc / 8, 8, k, ...) is the
+ * row's top-k (idx [B][ldc]: 0 .. N-1, then 0x7fffffff).
+ * Accepts 0 < B <= 65535, C a multiple of 32 with C <= 2048, 0 < N <= 2^20, ldf >= N,
+ * ldc >= N, xn and w_packed 16-byte aligned, no NULL pointer but logits; everything else is
+ * refused before any launch with the outputs untouched. */
+int zs_tag_conv(const void* xn, int B, int C, int dtype, const void* w_packed, int N,
+                const float* bias, float* frame, int ldf, float* clip, int ldc, float* logits,
+                void* stream);
+
 /* ------------------------------------------------------------------ CNN14 (cnns.py:36-78,171-201)
  * zs_conv3x3_bn_relu: NHWC implicit-GEMM conv3x3 pad 1 (no bias) + eval BN + ReLU.
  *   x [B][H][W][Cin] (dtype), w [Cout][3][3][Cin] (dtype), bn folded as scale/shift f32 [Cout]

@@ -4,8 +4,10 @@ Same constructor, same state-dict keys (parameters + relative_position_index / a
 buffers + audio_feats_extractor), ``forward(waveform) -> embedding [B, 768]`` like the reference
 (htsat.py:941-958 returns output_dict["embedding"]).  The forward is the zsaac HTSAT engine: fused
 log-mel+bn0, bicubic fold, patch-embed+LN, 12 Swin blocks (MFMA GEMMs, fused window attention),
-patch merging, final LN + mean-pool.  The dead tscam_conv / head branch is kept as parameters (so
-checkpoints load) but not computed: it does not feed ``embedding``.
+patch merging, final LN + mean-pool.  ``forward`` does not run the tscam_conv branch: it does not
+feed ``embedding``.  ``forward_features(image)`` does (htsat.py:830-894, the engine's tagging head:
+zs_tag_prep + zs_tag_conv) and returns the reference's four keys; ``head`` (commented out of the
+reference's forward_features) is kept as parameters only, so checkpoints load.
 
 Only the CLAP configuration of retrieval/models/audio_encoder.py:41-51 is supported.
 """
@@ -47,3 +49,27 @@ class HTSAT_Swin_Transformer(nn.Module):
         require_device(input, "HTSAT_Swin_Transformer.forward")
         eng = self._engine(input.shape[0], input.shape[1], input.device)
         return eng.encode(input.float().contiguous()).clone()
+
+    def reshape_wav2img(self, x):
+        """htsat.py:908-923: the bn0'd log-mel [B, 1, T <= 1024, 64] -> the folded image
+        [B, 1, 256, 256] (bicubic along time to 1024 frames, four 256-frame chunks stacked along
+        frequency), on the engine's zs_wav2img."""
+        from zsaac import ops
+        require_device(x, "HTSAT_Swin_Transformer.reshape_wav2img")
+        assert x.dim() == 4 and x.shape[1] == 1 and x.shape[3] == 64, x.shape
+        return ops.wav2img(x[:, 0].float().contiguous()).unsqueeze(1)
+
+    def forward_features(self, x):
+        """htsat.py:790-894 from the folded image [B, 1, 256, 256]: the reference's output_dict,
+        f32: ``embedding`` [B, 768], ``clipwise_output`` [B, 527], ``framewise_output``
+        [B, 1024, 527] and ``fine_grained_embedding`` [B, 1024, 768].  The last two are 32 frames
+        each repeated 32 times (``interpolate``, htsat.py:31-44).  The device computes and keeps
+        the 32-frame form; the repeat happens here, at the Python boundary (a [B, 1024, W] tensor
+        with repeated rows has no strided view, so it is one ``repeat_interleave`` copy)."""
+        require_device(x, "HTSAT_Swin_Transformer.forward_features")
+        assert x.dim() == 4 and tuple(x.shape[1:]) == (1, 256, 256), x.shape
+        out = self._engine(x.shape[0], 320000, x.device).events_img(x[:, 0].float())
+        return {"framewise_output": out.frame.repeat_interleave(32, dim=1),
+                "clipwise_output": out.clip.clone(),
+                "fine_grained_embedding": out.fine.repeat_interleave(32, dim=1),
+                "embedding": out.feat.clone()}

@@ -51,6 +51,8 @@ SIGNATURES = {
     "zs_swin_block": [P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "zs_patch_merge_ln": [P, I, I, I, I, P, P, P, I, P],
     "zs_ln_meanpool": [P, I, I, I, P, P, P, P],
+    "zs_tag_prep": [P, I, I, P, P, P, I, P, P],
+    "zs_tag_conv": [P, I, I, I, P, I, P, P, I, P, I, P, P],
     "zs_conv3x3_bn_relu": [P, I, I, I, I, P, I, P, P, P, I, P],
     "zs_avgpool2": [P, I, I, I, I, P, I, P],
     "zs_cnn_head": [P, I, I, I, I, P, I, P],

@@ -58,6 +58,30 @@ def pack_qkv(w: torch.Tensor, b: torch.Tensor, C: int):
     return pack_frags(wp), bp.contiguous()
 
 
+def pack_tscam(w: torch.Tensor) -> torch.Tensor:
+    """tscam_conv.weight [N][C][2][3] (htsat.py:7-8 of the drop-in; Conv2d(C, N, (2, 3))) -> the
+    [Np][6C] matrix of zs_tag_conv, column (c * 3 + d) * C + ch, Np = N rounded up to 16 with zero
+    rows, fragment-packed."""
+    N, C = w.shape[0], w.shape[1]
+    assert w.shape[2:] == (2, 3) and C % 32 == 0, w.shape
+    m = torch.zeros((N + 15) // 16 * 16, 6 * C, dtype=w.dtype, device=w.device)
+    m[:N] = w.permute(0, 2, 3, 1).reshape(N, 6 * C)
+    return pack_frags(m)
+
+
+class TagOutput:
+    """What ``HTSAT_Swin_Transformer.forward_features`` (htsat.py:887-892) returns, in the
+    32-frame form, as views of the encoder's buffers (valid until its next pass):
+    ``feat`` [B, 768] (`embedding`), ``emb`` [B, 1024] (ASE.encode_audio; None without
+    ``audio_proj``), ``clip`` [B, N] (`clipwise_output`), ``frame`` [B, 32, N] and ``fine``
+    [B, 32, 768] (`framewise_output` / `fine_grained_embedding` before their x32 repeat) and
+    ``tokens`` [B, 64, 768], the last stage's tokens before ``norm``."""
+
+    def __init__(self, feat, emb, clip, frame, fine, tokens):
+        self.feat, self.emb, self.clip, self.frame, self.fine, self.tokens = (
+            feat, emb, clip, frame, fine, tokens)
+
+
 def _f32(t, dev):
     return t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
@@ -171,6 +195,11 @@ class AudioEncoder:
         self.width = width
         # audio_proj is optional: the bare HTSAT/CNN14 drop-ins return the encoder features
         self.proj = AudioProjWeights(sd, self.dev, dtype) if "audio_proj.0.weight" in sd else None
+        # the tagging head (encode_events): the checkpoint's own tensors, repacked on first use
+        # into _tagw (shared with twins); _tagbuf: this encoder's head buffers
+        p = "audio_encoder.audio_enc.tscam_conv."
+        self._tscam = (sd.get(p + "weight"), sd.get(p + "bias"))
+        self._tagw, self._tagbuf = {}, None
         self._alloc()
 
     def twin(self, max_batch=None):
@@ -180,6 +209,7 @@ class AudioEncoder:
         if max_batch:
             t.B = int(max_batch)
         t._graphs = {}     # captured graphs read / write the parent's buffers: never shared
+        t._tagbuf = None   # head buffers (encode_events) are private too, made on first use
         t._alloc()
         return t
 
@@ -214,9 +244,10 @@ class AudioEncoder:
             self.c_b = torch.empty(big, device=dev, dtype=dtype)
 
     # -------------------------------------------------------------- HTSAT
-    def _htsat(self, B):
+    def _htsat(self, B, from_img=False):
         w = self.w
-        ops.wav2img(self.logmel[:B], out=self.img[:B])
+        if not from_img:           # events_img: self.img already holds the folded image
+            ops.wav2img(self.logmel[:B], out=self.img[:B])
         M, C, res = B * 4096, 96, 64
         x = self.x[:M * C].view(M, C)
         ops.patch_embed(self.img[:B], w.pe_w, w.pe_b, *w.pe_ln, out=x)
@@ -247,6 +278,7 @@ class AudioEncoder:
                 ops.gemm(y, mg["red_w"], nxt)
                 x, M, C, res = nxt, Mo, 2 * C, res // 2
         ops.ln_meanpool(x, B, res * res, C, *w.norm, out=self.feat[:B])
+        return x           # the last stage's tokens [B * 64, 768] (encode_events)
 
     # -------------------------------------------------------------- CNN14
     def _cnn14(self, B):
@@ -317,3 +349,76 @@ class AudioEncoder:
                  workspace=self.ws)
         ops.gemm(self.proj_h[:B], self.proj.w2, self.emb[:B], bias=self.proj.b2, workspace=self.ws)
         return ops.l2norm(self.emb[:B], out=self.emb[:B])
+
+    # -------------------------------------------------------------- tagging head (HTSAT)
+    def _tag_setup(self):
+        if self.kind != "htsat":
+            raise NotImplementedError("encode_events: the tagging head is HTSAT's (CNN14 has none)")
+        if not self._tagw:
+            w, b = self._tscam
+            if w is None or b is None:
+                raise KeyError("encode_events: the checkpoint holds no audio_encoder.audio_enc."
+                               "tscam_conv.weight / .bias (the HTSAT tagging head)")
+            self._tagw.update(n=int(w.shape[0]), b=_f32(b, self.dev),
+                              w=pack_tscam(_w(w, self.dev, self.dtype)))
+        if self._tagbuf is None:
+            B, dev, N = self.B, self.dev, self._tagw["n"]
+            ldc = (N + 7) // 8 * 8       # zs_sim_topk_finalize reads rows of ldc / 8 lists of 8
+            idx = torch.full((B, ldc), 0x7fffffff, device=dev, dtype=torch.int32)
+            idx[:, :N] = torch.arange(N, device=dev, dtype=torch.int32)
+            self._tagbuf = dict(
+                xn=torch.empty(B, 64, self.width, device=dev, dtype=self.dtype),
+                fine=torch.empty(B, 32, self.width, device=dev),
+                frame=torch.empty(B, 32, N, device=dev),
+                clip=torch.full((B, ldc), float("-inf"), device=dev), idx=idx,
+                top_v=torch.empty(B, 8, device=dev),
+                top_i=torch.empty(B, 8, device=dev, dtype=torch.int32))
+        return self._tagw, self._tagbuf
+
+    def events_logmel(self, logmel, B=None) -> TagOutput:
+        """encode_logmel plus the tagging head on the last stage's tokens (zs_tag_prep,
+        zs_tag_conv): -> TagOutput (views).  ``feat`` / ``emb`` are encode_logmel's, bit for bit."""
+        if logmel is not None:
+            self._tag_setup()      # refuse before any copy or launch
+            B = logmel.shape[0]
+            self.logmel[:B].copy_(logmel)
+        return self._events(B, False)
+
+    def events_img(self, img) -> TagOutput:
+        """events_logmel from the folded image [B, 256, 256] (what ``reshape_wav2img`` returns,
+        the input of ``forward_features``)."""
+        self._tag_setup()
+        B = img.shape[0]
+        assert B <= self.B and tuple(img.shape[1:]) == (256, 256), (img.shape, self.B)
+        self.img[:B].copy_(img)
+        return self._events(B, True)
+
+    def _events(self, B, from_img) -> TagOutput:
+        tw, tb = self._tag_setup()
+        tokens = self._htsat(B, from_img).view(B, 64, self.width)
+        emb = self.project(self.feat[:B]) if self.proj is not None else None
+        N = tw["n"]
+        ops.tag_prep(tokens, B, self.width, *self.w.norm, tb["xn"], tb["fine"])
+        ops.tag_conv(tb["xn"], B, self.width, tw["w"], N, tw["b"], tb["frame"], tb["clip"])
+        return TagOutput(self.feat[:B], emb, tb["clip"][:B, :N], tb["frame"][:B], tb["fine"][:B],
+                         tokens)
+
+    def encode_events(self, wav: torch.Tensor) -> TagOutput:
+        """wav [B, T] f32 (device) -> TagOutput: the embedding of :meth:`encode` and the clip-level
+        tags / frame-level sound events of the checkpoint's tscam_conv head."""
+        B = wav.shape[0]
+        assert B <= self.B and wav.shape[1] == self.T, (wav.shape, self.B, self.T)
+        self._tag_setup()          # refuse before any launch
+        ops.logmel(wav, self.tables, bn=self.w.bn0, out=self.logmel[:B])
+        return self.events_logmel(None, B)
+
+    def tag_topk(self, B, k):
+        """The k <= 8 most probable classes of each of the last events pass's B clips, on the
+        device (zs_sim_topk_finalize over the clip rows): (prob [B, k] f32, id [B, k] int32),
+        best first, ties to the lower id."""
+        tw, tb = self._tag_setup()
+        assert 1 <= k <= min(8, tw["n"]) and B <= self.B, (k, B)
+        ldc = tb["clip"].shape[1]
+        val, idx = tb["top_v"].view(-1)[:B * k].view(B, k), tb["top_i"].view(-1)[:B * k].view(B, k)
+        ops.sim_topk_finalize(tb["clip"], tb["idx"], B, ldc // 8, 8, k, val, idx)
+        return val, idx

@@ -269,6 +269,32 @@ def ln_meanpool(x, B, N, C, ln_w, ln_b, out):
     return out
 
 
+# ---------------------------------------------------------------- HTSAT tagging head
+def tag_prep(x, B, C, ln_w, ln_b, xn, fine):
+    """zs_tag_prep: final tokens x [B, 64, C] f32 -> xn [B, 64, C] (its dtype: the conv's operand)
+    and fine [B, 32, C] f32 (the mean of a frame's two frequency bins)."""
+    _need(x.dtype == torch.float32 and fine.dtype == torch.float32 and x.is_contiguous()
+          and xn.is_contiguous() and fine.is_contiguous() and x.numel() >= B * 64 * C
+          and xn.numel() >= B * 64 * C and fine.numel() >= B * 32 * C, "tag_prep: buffers")
+    call("zs_tag_prep", _p(x), B, C, _p(ln_w), _p(ln_b), _p(xn), dt(xn), _p(fine), _s())
+
+
+def tag_conv(xn, B, C, w_packed, N, bias, frame, clip, logits=None):
+    """zs_tag_conv: xn [B, 64, C] and the fragment-packed tscam_conv weight -> frame [B, 32, >= N]
+    and clip [B, >= N] f32 probabilities (row strides taken from the tensors; only columns
+    [0, N) are written), optionally the logits in frame's layout."""
+    _need(xn.dtype == w_packed.dtype and xn.is_contiguous() and w_packed.is_contiguous()
+          and xn.numel() >= B * 64 * C and w_packed.numel() >= (N + 15) // 16 * 16 * 6 * C,
+          "tag_conv: operands")
+    _need(frame.dtype == clip.dtype == torch.float32 and frame.dim() == 3 and clip.dim() == 2
+          and frame.shape[0] >= B and frame.shape[1] == 32 and clip.shape[0] >= B
+          and frame.stride(2) == 1 and clip.stride(1) == 1 and frame.stride(0) == 32 * frame.stride(1)
+          and (logits is None or (logits.dtype == torch.float32 and logits.shape == frame.shape
+                                  and logits.stride() == frame.stride())), "tag_conv: outputs")
+    call("zs_tag_conv", _p(xn), B, C, dt(xn), _p(w_packed), N, _p(bias), _p(frame), frame.stride(1),
+         _p(clip), clip.stride(0), _p(logits), _s())
+
+
 # ---------------------------------------------------------------- CNN14
 def conv3x3_bn_relu(x, B, H, W, Cin, w, Cout, scale, shift, out):
     call("zs_conv3x3_bn_relu", _p(x), B, H, W, Cin, _p(w), Cout, _p(scale), _p(shift), _p(out),
