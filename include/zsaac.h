@@ -106,6 +106,58 @@ int zs_resample_pack(const void* frames, int fmt, const long* offsets, const int
                      int T, const float* table, int num_zeros, int precision, float* out,
                      void* stream);
 
+/* zs_resample_windows: zs_resample_pack for recordings longer than T -- each recording is
+ * resampled once, straight into overlapping window rows.  The R recordings lie in `frames` as
+ * zs_resample_pack's clips do (offsets, n_frames, channels, sr_in, n_out: HOST arrays [R],
+ * validated here, kernel arguments; n_frames[r] is the WHOLE recording).  n_win[r] (host) is the
+ * number of window rows of recording r (zsaac.longform.window_plan; 0 writes no row).
+ * out [sum n_win][T] f32, recording-major: with row0[r] = sum of n_win before r,
+ *   out[row0[r] + w][t] = y_r[w * hop + t]   for w * hop + t < n_out[r], else exactly +0,
+ * y_r the signal zs_resample_pack writes for recording r with an unbounded T (downmix,
+ * kaiser_best, gain; the downmix alone at sr_in == sr_out).  The arithmetic of an output depends
+ * on its global index w * hop + t alone (held in 64 bits), so a window row is bit-equal to the
+ * same outputs of a zs_resample_pack row, whatever hop.
+ * One launch per 64 recordings (and per 65535 window rows); a block finds its recording from
+ * the per-recording row0 of its descriptor.
+ * Refuses, before the first launch and with `out` untouched, everything zs_resample_pack
+ * refuses and: hop <= 0; n_win[r] < 0; a last window without a valid output ((n_win[r] - 1) *
+ * hop >= max(n_out[r], 1) for n_win[r] > 1); a last input index n_out * sr_in / sr_out that does
+ * not fit an int; sum n_win not an int or sum n_win * T not a long. */
+int zs_resample_windows(const void* frames, int fmt, const long* offsets, const int* n_frames,
+                        const int* channels, const int* sr_in, const int* n_out, const int* n_win,
+                        int R, int sr_out, int T, int hop, const float* table, int num_zeros,
+                        int precision, float* out, void* stream);
+
+/* zs_window_stitch: the windows' head outputs back onto one time line per recording (the back
+ * of the windowed pass zs_resample_windows starts).  Device tables: plan [R][4] int32 = (row0,
+ * n_win, frow0, F) per recording -- its first window row, its windows, its first time-line row
+ * and its time-line frames, frow0 ascending with frow0[r + 1] = frow0[r] + F[r] -- and wgt [W]
+ * f32, window row i's share of valid samples v / T.  Window w's head frame j is time-line frame
+ * w * hop_f + j (hop_f = hop / (T / 32) head frames).
+ *   timeline[frow0 + f][k] (k < N) = the mean over the windows w with 0 <= f - w * hop_f < 32 of
+ *     frame[row0 + w][f - w * hop_f][k]: added in ascending w in f32, then divided by their
+ *     count c (1 <= c <= ceil(32 / hop_f)); c == 1 copies the value.
+ *   rec_clip[r][k] = max_w clip[row0 + w][k] for k < N; columns [N, ldrc) are written -inf, so
+ *     with ldrc % 8 == 0 zs_sim_topk_finalize(rec_clip, idx, R, ldrc / 8, 8, k, ...) is the
+ *     recording's top-k.
+ *   rec_emb[r][0..K) = s / max(||s||, 1e-12), s = sum_w wgt[row0 + w] * emb[row0 + w] in
+ *     ascending w in f32 (product rounded, then added), the norm reduced in zs_l2norm_rows'
+ *     order; n_win == 1 copies the row bit for bit.
+ * frame [W][32][ldf], clip [W][ldc], emb [W][lde], timeline [sum F][ldt], rec_clip [R][ldrc],
+ * rec_emb [R][ldre], all f32; an input / output pair may be NULL.  Only columns [0, N) of a
+ * time-line row and [0, K) of an embedding row are written.  16-byte accesses where ldf and ldt
+ * are multiples of 4 and frame / timeline 16-byte aligned, scalar ones otherwise.  No atomics,
+ * fixed orders: a recording's outputs are bit-identical whatever R and whichever recordings
+ * share the launch.
+ * Refuses before any launch: R <= 0; hop_f outside [1, 32]; N <= 0; a leading dimension below
+ * N (frame, clip, timeline, rec_clip) or K (emb, rec_emb); K not a multiple of 32 or > 2048; a
+ * NULL plan / wgt (plan 16-byte aligned); an output without its input; no output at all.  The
+ * plan's contents are the host's to check when it builds it (zsaac.longform.stitch_tables). */
+int zs_window_stitch(const int* plan, const float* wgt, int R, int hop_f, int N,
+                     const float* frame, int ldf, const float* clip, int ldc, const float* emb,
+                     int lde, int K, float* timeline, int ldt, float* rec_clip, int ldrc,
+                     float* rec_emb, int ldre, void* stream);
+
 /* zs_patch_embed: htsat.py:115-125 PatchEmbed (Conv2d 1->96, k4 s4) + LayerNorm(96):
  * img [B][256][256] f32 -> x [B*4096][96] f32 (token = row*64 + col of the 64x64 patch grid).
  * Accepts 0 < B <= 32767; non-NULL buffers. */

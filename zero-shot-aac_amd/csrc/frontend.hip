@@ -693,6 +693,95 @@ __global__ __launch_bounds__(256) void resample_pack_kernel(
   }
 }
 
+// ------------------------------------------------------------------ resample into window rows
+// The same signal cut into overlapping windows of one recording: window w of recording r holds
+// its outputs [w * hop, w * hop + T), zero past n_out.  A sibling of resample_pack_kernel: the
+// arithmetic of output t (n, r, the two table phases, the clamps imax / kmax, rs_wing, the gain)
+// depends on the GLOBAL index t alone, not on the tile or the row it falls in, so a window row
+// is bit-equal to the same outputs of a resample_pack row.  The window's first output g0 is a
+// 64-bit quantity (p = t * sr_in already is).
+struct RsRec {
+  long off;        // first sample of the recording in the flat buffer
+  int n_frames;    // frames present
+  int channels;
+  int sr_in;
+  int n_out;       // outputs of the whole recording
+  int step, wing, stride;   // as in RsClip
+  int row0;        // first window row of the recording, relative to the launch's first row
+  int n_win;
+  int pad_;
+};
+struct RsRecBatch { RsRec c[RS_MAX_CLIPS]; };
+
+template <bool S16>
+__global__ __launch_bounds__(256) void resample_windows_kernel(
+    const void* __restrict__ frames, const RsRecBatch batch, int nc, long rowbase, int y0,
+    int sr_out, int T, int hop, const float2* __restrict__ table, int nwin, int nb,
+    float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float rs_x[];
+  const int wrow = y0 + blockIdx.y;        // window row within this batch of recordings
+  int j = 0;                               // the recording that owns it (host: one always does)
+  while (j + 1 < nc && !(wrow >= batch.c[j].row0 && wrow < batch.c[j].row0 + batch.c[j].n_win)) ++j;
+  const RsRec& cl = batch.c[j];
+  const long off = cl.off;
+  const int n_frames = cl.n_frames, C = cl.channels, sr_in = cl.sr_in;
+  const long g0 = (long)(wrow - cl.row0) * hop;   // the window's first output
+  float* row = out + (rowbase + wrow) * T;
+  const int t0 = blockIdx.x * RS_TILE;
+  const int t1 = min(t0 + RS_TILE, T);
+  // outputs [t0, tv) of the window are computed, [tv, t1) are zero
+  const int tv = (int)max(0L, min((long)t1, (long)cl.n_out - g0));
+  if (tv <= t0) {
+    for (int t = t0 + threadIdx.x; t < t1; t += 256) row[t] = 0.f;
+    return;
+  }
+  if (sr_in == sr_out) {                   // the downmix alone
+    for (int t = t0 + threadIdx.x; t < t1; t += 256)
+      row[t] = (t < tv && g0 + t < n_frames) ? rs_downmix<S16>(frames, off + (g0 + t) * C, C) : 0.f;
+    return;
+  }
+  const int step = cl.step, W = cl.wing;
+  const int n_lo = (int)((g0 + t0) * sr_in / sr_out);
+  const int n_hi = (int)((g0 + tv - 1) * sr_in / sr_out);
+  const int s0 = n_lo - W + 1;             // input sample held by rs_x[0]
+  const int span = n_hi - n_lo + 2 * W;    // host: span <= the launch's LDS floats
+  for (int i = threadIdx.x; i < span; i += 256) {
+    const int m = s0 + i;
+    rs_x[i] = (m >= 0 && m < n_frames) ? rs_downmix<S16>(frames, off + (long)m * C, C) : 0.f;
+  }
+  __syncthreads();
+  const int D = max(sr_in, sr_out);
+  const float inv_d = 1.0f / (float)D;
+  const float gain = sr_out < sr_in ? (float)((double)sr_out / (double)sr_in) : 1.0f;
+  const int stride = cl.stride;
+  for (int q = threadIdx.x; q < RS_TILE; q += 256) {
+    const int t = t0 + ((q * stride) & (RS_TILE - 1));
+    if (t >= t1) continue;
+    float y = 0.f;
+    if (t < tv) {
+      const long p = (g0 + t) * sr_in;
+      const int n = (int)(p / sr_out), r = (int)(p % sr_out);
+      const float* xc = rs_x + (n - s0);   // x[n]
+      {                                    // left wing: x[n - i]
+        const long ph = (long)nb * r;
+        const int o = (int)(ph / D);
+        const float eta = (float)(int)(ph % D) * inv_d;
+        const int imax = min(n + 1, (nwin - o) / step);
+        y = rs_wing<-1>(table + o, step, eta, xc, imax);
+      }
+      {                                    // right wing: x[n + 1 + k]
+        const long ph = (long)nb * (sr_out - r);
+        const int o = (int)(ph / D);
+        const float eta = (float)(int)(ph % D) * inv_d;
+        const int kmax = min(n_frames - n - 1, (nwin - o) / step);
+        y += rs_wing<1>(table + o, step, eta, xc + 1, kmax);
+      }
+      y *= gain;
+    }
+    row[t] = y;
+  }
+}
+
 }  // namespace zs
 
 using namespace zs;
@@ -754,6 +843,87 @@ extern "C" int zs_resample_pack(const void* frames, int fmt, const long* offsets
       hipLaunchKernelGGL(resample_pack_kernel<false>, grid, dim3(256), lds * sizeof(float), S(stream),
                          frames, batch, b0, sr_out, T, tab, nwin, nb, out);
     ZS_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int zs_resample_windows(const void* frames, int fmt, const long* offsets,
+                                   const int* n_frames, const int* channels, const int* sr_in,
+                                   const int* n_out, const int* n_win, int R, int sr_out, int T,
+                                   int hop, const float* table, int num_zeros, int precision,
+                                   float* out, void* stream) {
+  ZS_REQUIRE(frames && offsets && n_frames && channels && sr_in && n_out && n_win && table && out,
+             "zs_resample_windows: NULL buffer");
+  ZS_REQUIRE(R > 0 && T > 0, "zs_resample_windows: R > 0, T > 0");
+  ZS_REQUIRE(hop > 0, "zs_resample_windows: hop > 0");
+  ZS_REQUIRE(fmt == 0 || fmt == 1, "zs_resample_windows: fmt %d (0: f32, 1: s16)", fmt);
+  ZS_REQUIRE(sr_out >= 1 && sr_out <= (1 << 24), "zs_resample_windows: 1 <= sr_out <= 2^24");
+  ZS_REQUIRE(num_zeros >= 1 && num_zeros <= 1024 && precision >= 0 && precision <= 12,
+             "zs_resample_windows: 1 <= num_zeros <= 1024, 0 <= precision <= 12");
+  ZS_REQUIRE(((uintptr_t)table & 7) == 0, "zs_resample_windows: table 8-byte aligned");
+  const int nb = 1 << precision, nwin = nb * num_zeros + 1;
+  // every recording is checked before the first launch
+  long rows = 0;
+  for (int b = 0; b < R; ++b) {
+    ZS_REQUIRE(channels[b] >= 1 && channels[b] <= RS_MAX_CH,
+               "zs_resample_windows: recording %d has %d channels (1..%d)", b, channels[b], RS_MAX_CH);
+    ZS_REQUIRE(sr_in[b] >= 1 && sr_in[b] <= (1 << 24),
+               "zs_resample_windows: recording %d: 1 <= sr_in <= 2^24", b);
+    ZS_REQUIRE((long)sr_in[b] <= 8L * sr_out && (long)sr_out <= 8L * sr_in[b],
+               "zs_resample_windows: recording %d: %d Hz -> %d Hz is beyond a factor of 8", b, sr_in[b], sr_out);
+    ZS_REQUIRE(n_frames[b] >= 0 && n_out[b] >= 0 && offsets[b] >= 0,
+               "zs_resample_windows: recording %d: negative length or offset", b);
+    ZS_REQUIRE(n_win[b] >= 0, "zs_resample_windows: recording %d: n_win %d < 0", b, n_win[b]);
+    ZS_REQUIRE(n_win[b] <= 1 || (long)(n_win[b] - 1) * hop < (long)std::max(n_out[b], 1),
+               "zs_resample_windows: recording %d: window %d starts at output %ld of %d (no valid output)",
+               b, n_win[b] - 1, (long)(n_win[b] - 1) * hop, n_out[b]);
+    ZS_REQUIRE((long)T * sr_in[b] / sr_out < 0x7fffffffL,
+               "zs_resample_windows: recording %d: T * sr_in / sr_out does not fit an int", b);
+    ZS_REQUIRE((long)n_out[b] * sr_in[b] / sr_out < 0x7fffffffL,
+               "zs_resample_windows: recording %d: n_out * sr_in / sr_out does not fit an int", b);
+    const int step = sr_out < sr_in[b] ? (int)((long)nb * sr_out / sr_in[b]) : nb;
+    ZS_REQUIRE(step >= 1, "zs_resample_windows: recording %d: table step 0 (precision %d too low for %d Hz -> %d Hz)",
+               b, precision, sr_in[b], sr_out);
+    const long span = (long)(RS_TILE - 1) * sr_in[b] / sr_out + 2L * ((nwin - 1) / step + 1) + 2;
+    ZS_REQUIRE(span * 4 <= 65536, "zs_resample_windows: recording %d: a tile's input span (%ld floats) exceeds 64 KB of LDS", b, span);
+    rows += n_win[b];
+    ZS_REQUIRE(rows < 0x7fffffffL && rows <= 0x7fffffffffffffffL / T,
+               "zs_resample_windows: sum n_win (an int) times T does not fit a long");
+  }
+  long rowbase = 0;
+  for (int b0 = 0; b0 < R; b0 += RS_MAX_CLIPS) {
+    const int nc = std::min(RS_MAX_CLIPS, R - b0);
+    RsRecBatch batch = {};
+    long lds = 0, nrows = 0;
+    for (int j = 0; j < nc; ++j) {
+      const int b = b0 + j;
+      RsRec& c = batch.c[j];
+      c.off = offsets[b];
+      c.n_frames = n_frames[b];
+      c.channels = channels[b];
+      c.sr_in = sr_in[b];
+      c.n_out = n_out[b];
+      c.step = sr_out < sr_in[b] ? (int)((long)nb * sr_out / sr_in[b]) : nb;
+      c.wing = (nwin - 1) / c.step + 1;
+      c.stride = rs_stride(sr_in[b], sr_out);
+      c.row0 = (int)nrows;
+      c.n_win = n_win[b];
+      nrows += n_win[b];
+      if (sr_in[b] != sr_out)
+        lds = std::max(lds, (long)(RS_TILE - 1) * sr_in[b] / sr_out + 2L * c.wing + 2);
+    }
+    const float2* tab = reinterpret_cast<const float2*>(table);
+    for (long y0 = 0; y0 < nrows; y0 += 65535) {       // grid.y holds at most 65535 rows
+      const dim3 grid(cdiv(T, RS_TILE), (unsigned)std::min(65535L, nrows - y0));
+      if (fmt == 1)
+        hipLaunchKernelGGL(resample_windows_kernel<true>, grid, dim3(256), lds * sizeof(float), S(stream),
+                           frames, batch, nc, rowbase, (int)y0, sr_out, T, hop, tab, nwin, nb, out);
+      else
+        hipLaunchKernelGGL(resample_windows_kernel<false>, grid, dim3(256), lds * sizeof(float), S(stream),
+                           frames, batch, nc, rowbase, (int)y0, sr_out, T, hop, tab, nwin, nb, out);
+      ZS_LAUNCH_CHECK();
+    }
+    rowbase += nrows;
   }
   return 0;
 }

@@ -40,6 +40,8 @@ SIGNATURES = {
     "zs_wav2img": [P, I, I, P, P],
     "zs_pack_clips": [P, P, P, I, I, P, P],
     "zs_resample_pack": [P, I, P, P, P, P, P, I, I, I, P, I, I, P, P],
+    "zs_resample_windows": [P, I, P, P, P, P, P, P, I, I, I, I, P, I, I, P, P],
+    "zs_window_stitch": [P, P, I, I, I, P, I, P, I, P, I, I, P, I, P, I, P, I, P],
     "zs_patch_embed": [P, I, P, P, P, P, P, P],
     "zs_layernorm": [P, I, I, I, P, P, P, F, P, I, I, P],
     "zs_gemm": [I, I, I, I, P, I, P, I, P, P, I, P, I, I, I, I, P, P],

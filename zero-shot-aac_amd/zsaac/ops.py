@@ -99,6 +99,77 @@ def resample_pack(frames, offsets, n_frames, channels, sr_in, n_out, sr_out, T, 
     return out[:B]
 
 
+def resample_windows(frames, offsets, n_frames, channels, sr_in, n_out, n_win, sr_out, T, hop,
+                     table, num_zeros, precision, out):
+    """Decoded recordings -> out [sum n_win, T]: each recording resampled once (as
+    :func:`resample_pack` does, without the crop) and cut into ``n_win[r]`` windows of T outputs
+    ``hop`` apart, zero past its end (zs_resample_windows).  The six per-recording sequences live
+    on the host; ``n_win`` from ``longform.window_plan``."""
+    import numpy as np
+    _need(frames.dtype in (torch.float32, torch.int16) and frames.is_contiguous(),
+          "resample_windows: frames float32 or int16, contiguous")
+    _need(table.dtype == torch.float32 and table.is_contiguous()
+          and table.numel() == 2 * ((num_zeros << precision) + 1),
+          "resample_windows: table [(num_zeros << precision) + 1, 2] float32")
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    meta = [np.ascontiguousarray(a, dtype=np.int32) for a in (n_frames, channels, sr_in, n_out, n_win)]
+    R = off.shape[0]
+    _need(R > 0 and all(a.shape == (R,) for a in meta), "resample_windows: six sequences of length R")
+    rows = int(meta[4].astype(np.int64).sum())
+    _need(bool((meta[4] >= 0).all()) and out.dtype == torch.float32 and out.is_contiguous()
+          and out.dim() == 2 and out.shape[0] >= rows and out.shape[1] == T,
+          "resample_windows: out [sum n_win, T] float32")
+    end = off + meta[0].astype(np.int64) * meta[1]
+    _need(bool((off >= 0).all()) and bool((meta[0] >= 0).all()) and int(end.max()) <= frames.numel(),
+          "resample_windows: a recording lies outside the frame buffer")
+    call("zs_resample_windows", _p(frames), 1 if frames.dtype == torch.int16 else 0, off.ctypes.data,
+         *[a.ctypes.data for a in meta], R, int(sr_out), T, int(hop), _p(table), num_zeros,
+         precision, _p(out), _s())
+    return out[:rows]
+
+
+def window_stitch(plan, plan_host, wgt, hop_f, N, frame=None, clip=None, emb=None, timeline=None,
+                  rec_clip=None, rec_emb=None):
+    """zs_window_stitch: per-window head outputs -> per-recording time line (mean over the
+    windows covering a frame), clip maxima and pooled, normalised embedding.  ``plan`` [R, 4]
+    int32 on the device and ``plan_host`` its host copy (``longform.stitch_tables``), checked
+    here against the tensors' shapes; ``wgt`` [W] f32 on the device.  frame [W, 32, >= N], clip
+    [W, >= N], emb [W, >= K]; timeline [sum F, >= N], rec_clip [R, >= N], rec_emb [R, >= K]; row
+    strides are taken from the tensors."""
+    import numpy as np
+    ph = np.asarray(plan_host)
+    _need(ph.ndim == 2 and ph.shape[1] == 4 and ph.shape[0] > 0 and plan.dtype == torch.int32
+          and plan.is_contiguous() and tuple(plan.shape) == ph.shape and wgt.dtype == torch.float32
+          and wgt.is_contiguous(), "window_stitch: plan [R, 4] int32 (device and host), wgt f32")
+    R = ph.shape[0]
+    ph = ph.astype(np.int64)
+    W, SF = int((ph[:, 0] + ph[:, 1]).max()), int(ph[-1, 2] + ph[-1, 3])
+    _need(bool((ph >= 0).all()) and bool((ph[1:, 2] == ph[:-1, 2] + ph[:-1, 3]).all())
+          and bool((ph[:, 3] <= np.maximum(ph[:, 1] - 1, 0) * hop_f + 32 * (ph[:, 1] > 0)).all())
+          and wgt.numel() >= W, "window_stitch: plan rows (row0, n_win, frow0, F) inconsistent")
+
+    def rows(t, n, name, d=2):
+        _need(t is None or (t.dtype == torch.float32 and t.dim() == d and t.stride(d - 1) == 1
+                            and t.shape[0] >= n), f"window_stitch: {name}")
+    rows(frame, W, "frame [W, 32, ldf]", 3)
+    _need(frame is None or (frame.shape[1] == 32 and frame.stride(0) == 32 * frame.stride(1)),
+          "window_stitch: frame [W, 32, ldf], windows contiguous")
+    rows(clip, W, "clip [W, ldc]"), rows(emb, W, "emb [W, lde]")
+    rows(timeline, SF, "timeline [sum F, ldt]"), rows(rec_clip, R, "rec_clip [R, ldrc]")
+    rows(rec_emb, R, "rec_emb [R, ldre]")
+    K = rec_emb.shape[1] if rec_emb is not None else 0
+    _need(timeline is None or timeline.shape[1] >= N, "window_stitch: timeline narrower than N")
+    _need(rec_clip is None or rec_clip.stride(0) == rec_clip.shape[1],
+          "window_stitch: rec_clip rows are written whole (-inf past N): no row padding")
+    _need(rec_emb is None or emb is None or emb.shape[1] >= K, "window_stitch: emb narrower than rec_emb")
+
+    def ld(t, d=0):
+        return t.stride(d) if t is not None else 0
+    call("zs_window_stitch", _p(plan), _p(wgt), R, int(hop_f), int(N), _p(frame), ld(frame, 1),
+         _p(clip), ld(clip), _p(emb), ld(emb), K, _p(timeline), ld(timeline), _p(rec_clip),
+         ld(rec_clip), _p(rec_emb), ld(rec_emb), _s())
+
+
 def wav2img(logmel_t, out=None):
     B, T_in, F = logmel_t.shape
     _need(F == 64, "wav2img expects 64 mel bins")

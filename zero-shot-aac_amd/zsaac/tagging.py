@@ -16,7 +16,8 @@ time frames.  Only the [B, k, 32] slice of the frame probabilities travels to th
 run-finding (:func:`segments`) is a pure host function.
 
 ``python -m zsaac.tagging --ckpt CLAP.pt [--labels class_labels_indices.csv] [--k 5]
-[--threshold 0.5] files...`` prints one JSON line per file.
+[--threshold 0.5] files...`` prints one JSON line per file.  Like the reference's evaluation it
+looks at the first 10 s of a file; ``zsaac.longform`` covers a recording's whole duration.
 """
 from __future__ import annotations
 
