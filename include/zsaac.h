@@ -348,7 +348,13 @@ int zs_prompt_assemble(const float* emb, int B, int D, const float* labels, int 
  * zs_row_attention: per row b, per head h: softmax(scale * q_i . k_j) v_j over j < len[b]
  * (causal: j <= i).  q element (b, i, h, d) at q[(b*L + i)*ldq + h*hd + d], k/v likewise with
  * ldkv, out with ldo (all dtype).  Serves models/mapper.py:49-66 (non-causal, hd 96) and the GPT-2
- * prompt prefill (causal, hd 64).  L <= 128, hd <= 128. */
+ * prompt prefill (causal, hd 64).  hd 64 or 96, L <= 256 and 2 * L * hd * 4 bytes of K / V <= 160
+ * KiB of LDS (hd 64: L <= 256; hd 96: L <= 213).  Above 64 KiB (L > 128 at hd 64, L > 85 at hd 96)
+ * the launch asks for more dynamic LDS than a kernel gets by default; it is served without a
+ * hipFuncSetAttribute call (tests/test_gpu_attn_kernels.py runs L = 130 and 256 against float64).
+ * Query rows i >= len[b] are written too (causal: over the len[b] keys).  bf16 with hd 64,
+ * L <= 32, ldq % 8 == ldkv % 8 == 0 and ldo % 4 == 0 runs the MFMA kernel, which rounds the
+ * unnormalised probabilities to bf16 before P.V. */
 int zs_row_attention(const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int L,
                      const int* len, int heads, int hd, int causal, float scale, void* out, int ldo,
                      int dtype, void* stream);
