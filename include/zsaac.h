@@ -896,6 +896,81 @@ int zs_beam_step(const float* part_stat, const float* part_val, const int* part_
                  int* kvrow, int* kvrow_tmp, int Lmax, int* pos, int* next_tok, int* all_done,
                  void* stream);
 
+/* ------------------------------------------------------------------ training the MLP mapper
+ * The backward pass behind the teacher-forced cross-entropy (train_prompt.py:133 over
+ * ClapCaption_prompt.forward, caption_model.py:297-313) with GPT-2 frozen, AdamW and the
+ * training-side noise.  Every matrix product of the backward pass is zs_gemm on
+ * a transposed operand (zs_transpose_cast); the entries below are what is not a GEMM.  None uses
+ * an atomic; every reduction runs in a fixed order (bit-identical results from run to run).
+ *
+ * zs_attention_bwd: the backward of GPT2Attention's causal softmax(Q K^T / 8) V (transformers,
+ * reached from caption_model.py:308) on the packed qkv [B*L][3*heads*64] the forward reads, given
+ * d_out [B*L][heads*64]:  P = softmax(Q K^T / 8) over j <= i recomputed per (b, head),
+ * dP = dO V^T, D_i = sum_j P_ij dP_ij (= dO_i . O_i), dV = P^T dO, dS = P o (dP - D),
+ * dQ = dS K / 8, dK = dS^T Q / 8, into dqkv in qkv's packing (all dtype, f32 arithmetic).  Rows
+ * i >= len[b] (len NULL: L) are ignored as queries and as keys, are never read, and get zeros.
+ * Head dim 64, 1 <= L <= 256; the three buffers 16-byte aligned, dqkv distinct from the inputs. */
+int zs_attention_bwd(const void* qkv, const void* d_out, int B, int L, const int* len, int heads,
+                     void* dqkv, int dtype, void* stream);
+
+/* zs_layernorm_bwd: dx of y = LayerNorm(x) g + b (GPT-2 ln_1 / ln_2 / ln_f) from x and dy:
+ * a = dy o g (g NULL: 1), dx = rstd (a - mean(a) - xhat mean(a o xhat)) + res (res NULL: 0; res
+ * may be dx).  rows != NULL (ln_f of the scored rows, as zs_layernorm's rows): row m of dy is the
+ * gradient of row rows[m] of x, and dx / res are addressed by rows[m] too; rows that repeat must
+ * carry equal results (the caller zeroes dx first; rows not named stay untouched). */
+int zs_layernorm_bwd(const float* x, int M, int C, int ldx, const int* rows, const float* dy,
+                     int ldy, const float* g, float eps, const float* res, int ldr, float* dx,
+                     int ldd, void* stream);
+
+/* zs_gelu_tanh_bwd: du = gelu_new'(u) dh from the pre-activation u (HF GPT2MLP's activation,
+ * which zs_gemm's ACT_GELU_TANH fuses); u / du dtype, dh f32. */
+int zs_gelu_tanh_bwd(const void* u, const float* dh, long n, void* du, int dtype, void* stream);
+/* zs_tanh_bwd: dpre = (1 - h^2) dh, the mapper's nn.Tanh (mapper.py:6-18) from its output h. */
+int zs_tanh_bwd(const float* h, const float* dh, long n, float* dpre, void* stream);
+
+/* zs_nll_grad_rows: the gradient of the mean cross-entropy (train_prompt.py:133) at the LM
+ * head's input rows, from mix[m] = sum_v softmax(logit[m])_v wte[v] (zs_memory_project +
+ * zs_memory_merge over the bank wte, scale 1, not normalised):
+ *   dhf[m] = (mix[m] - wte[tgt[m]]) / sum_b cnt[b], zeros for tgt[m] outside [0, V);
+ * cnt [B] are the device's caption lengths (zs_nll_finalize). */
+int zs_nll_grad_rows(const float* mix, int ldm, const void* wte, int V, int K, const int* tgt,
+                     const int* cnt, int B, int M, float* dhf, int ldd, int dtype, void* stream);
+/* zs_nll_loss: loss[0] = -sum_b sum[b] / sum_b cnt[b] of zs_nll_finalize's per-caption sums,
+ * the batch's mean token cross-entropy (train_prompt.py:133), on the device. */
+int zs_nll_loss(const float* sum, const int* cnt, int B, float* loss, void* stream);
+/* zs_soft_grad_rows: d_soft[b][j*D + d] = dx[(b*Smax + H_b + j)*D + d], j < n_soft: the
+ * residual-stream gradient at the soft-prefix rows of zs_gpt2_score_embed's layout (the
+ * backward of the concatenation, caption_model.py:303-306); H_b = hard_len[b] cut to [0, h_cap]. */
+int zs_soft_grad_rows(const float* dx, const int* hard_len, int h_cap, int n_soft, int B, int Smax,
+                      int D, float* d_soft, int ld, void* stream);
+
+/* zs_colsum: out[n] = sum_b x[b][n] in row order (the bias gradients of the mapper's two
+ * nn.Linear, mapper.py:6-18). */
+int zs_colsum(const float* x, int B, int N, int ldx, float* out, void* stream);
+/* zs_transpose_cast: y [C][Rp] (dtype) = x [R][C]^T (f32), Rp = R rounded up to 32, columns
+ * R .. Rp-1 zero: the operand form zs_gemm takes for dX = dY W (a transposed weight) and for
+ * dW = dY^T X (K = the padded batch). */
+int zs_transpose_cast(const float* x, int R, int C, int ldx, void* y, int Rp, int dtype,
+                      void* stream);
+
+/* zs_adamw: one torch.optim.AdamW update (train_prompt.py:104) of n elements on the f32 master
+ * p with moments m, v:  p *= 1 - lr wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
+ * p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps);  step >= 1.  operand (may be
+ * NULL): the dtype copy the forward's GEMMs read, refreshed from the new p.  step_ctr (may be
+ * NULL): step_ctr[0] = step. */
+int zs_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
+             float beta2, float eps, float weight_decay, int step, void* operand, int dtype,
+             int* step_ctr, void* stream);
+
+/* zs_noise_inject: noise_injection (utils.py:19-31): variance == 0 copies x to out; else
+ * out = normalize(normalize(x) + sqrt(variance) n), n ~ N(0, 1) iid (F.normalize, eps 1e-12).
+ * n of row r, columns 4c .. 4c+3: Philox4x32-10 with key = seed and counter (row_id[r] (NULL: r),
+ * step_ctr[0] (NULL: 0), c, 0); words (0, 1) and (2, 3) each give two normals by Box-Muller,
+ * u1 = ((w >> 8) + 1) 2^-24, u2 = (w' >> 8) 2^-24, (r cos, r sin)(2 pi u2), r = sqrt(-2 ln u1).
+ * A row's noise depends on its id and the step, not on its slot in the launch.  out may be x. */
+int zs_noise_inject(const float* x, int B, int D, int ldx, const int* row_id, const int* step_ctr,
+                    long seed, float variance, float* out, int ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

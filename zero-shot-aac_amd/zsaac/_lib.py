@@ -117,6 +117,17 @@ SIGNATURES = {
     "zs_mistral_decode_attention": [P, I, L, I, I, I, P, P, P, P, P, I, P, I, P],
     "zs_magic_score_t": [P, P, P, P, I, I, I, I, I, F, F, F, F, P, P],
     "zs_magic_step": [P, P, I, I, I, I, I, I, I, P, P, P, P, P, I, P, I, P, P, P, P, P, I, P],
+    "zs_attention_bwd": [P, P, I, I, P, I, P, I, P],
+    "zs_layernorm_bwd": [P, I, I, I, P, P, I, P, F, P, I, P, I, P],
+    "zs_gelu_tanh_bwd": [P, P, L, P, I, P],
+    "zs_tanh_bwd": [P, P, L, P, P],
+    "zs_nll_grad_rows": [P, I, P, I, I, P, P, I, I, P, I, I, P],
+    "zs_nll_loss": [P, P, I, P, P],
+    "zs_soft_grad_rows": [P, P, I, I, I, I, I, P, I, P],
+    "zs_colsum": [P, I, I, I, P, P],
+    "zs_transpose_cast": [P, I, I, I, P, I, I, P],
+    "zs_adamw": [P, P, P, P, L, F, F, F, F, F, I, P, I, P, P],
+    "zs_noise_inject": [P, I, I, I, P, P, L, F, P, I, P],
 }
 
 _lib = None

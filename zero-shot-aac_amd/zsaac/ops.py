@@ -904,3 +904,136 @@ def gpt2_decode_phase_window(*args, first, last, grid=96, f32=False):
     finally:
         call("zs_tune_set", b"dg_win_lo", 0)
         call("zs_tune_set", b"dg_win_hi", DECODE_PHASE_LAUNCHES)
+
+
+# ---------------------------------------------------------------- training (csrc/train.hip)
+def _f32c(*ts):
+    return all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in ts)
+
+
+def attention_bwd(qkv, d_out, B, L, heads, dqkv, lens=None):
+    """zs_attention_bwd: dqkv (qkv's packing) of the causal hd-64 attention from d_out
+    [B*L, heads*64]; rows >= lens[b] are never read and get zeros."""
+    _i32(lens, "lens")
+    _need(qkv.dtype == d_out.dtype == dqkv.dtype and qkv.is_contiguous() and d_out.is_contiguous()
+          and dqkv.is_contiguous(), "attention_bwd: one dtype, contiguous buffers")
+    _need(qkv.numel() >= B * L * 3 * heads * 64 and dqkv.numel() >= B * L * 3 * heads * 64
+          and d_out.numel() >= B * L * heads * 64 and (lens is None or lens.numel() >= B),
+          "attention_bwd: buffer sizes")
+    call("zs_attention_bwd", _p(qkv), _p(d_out), B, L, _p(lens), heads, _p(dqkv), dt(qkv), _s())
+    return dqkv
+
+
+def layernorm_bwd(x, dy, dx, g=None, residual=None, eps=1e-5, rows=None, M=None):
+    """zs_layernorm_bwd: dx = dLayerNorm(x)(dy * g) (+ residual); rows: dy row m belongs to row
+    rows[m] of x / residual / dx (dx zeroed by the caller)."""
+    C = x.shape[-1]
+    M = M if M is not None else (rows.numel() if rows is not None else dy.numel() // C)
+    _i32(rows, "rows")
+    _need(x.dim() == 2 and dy.dim() == 2 and dx.dim() == 2 and dy.shape[1] == C and dx.shape[1] == C
+          and x.dtype == dy.dtype == dx.dtype == torch.float32 and dy.shape[0] >= M
+          and x.stride(1) == dy.stride(1) == dx.stride(1) == 1, "layernorm_bwd: f32 [*, C] buffers")
+    _need(g is None or (g.dtype == torch.float32 and g.numel() == C), "layernorm_bwd: g is [C] f32")
+    _need(residual is None or (residual.dtype == torch.float32 and residual.dim() == 2
+                               and residual.shape == dx.shape and residual.stride(1) == 1),
+          "layernorm_bwd: residual like dx")
+    _need(rows is not None or (x.shape[0] >= M and dx.shape[0] >= M), "layernorm_bwd: rows")
+    call("zs_layernorm_bwd", _p(x), M, C, x.stride(0), _p(rows), _p(dy), dy.stride(0), _p(g),
+         float(eps), _p(residual), residual.stride(0) if residual is not None else 0, _p(dx),
+         dx.stride(0), _s())
+    return dx
+
+
+def gelu_tanh_bwd(u, dh, du):
+    """zs_gelu_tanh_bwd: du = gelu_new'(u) * dh (u / du one dtype, dh f32)."""
+    _need(u.dtype == du.dtype and dh.dtype == torch.float32 and u.numel() == dh.numel() == du.numel()
+          and u.is_contiguous() and dh.is_contiguous() and du.is_contiguous(), "gelu_tanh_bwd: buffers")
+    call("zs_gelu_tanh_bwd", _p(u), _p(dh), u.numel(), _p(du), dt(u), _s())
+    return du
+
+
+def tanh_bwd(h, dh, dpre):
+    """zs_tanh_bwd: dpre = (1 - h^2) * dh, all f32."""
+    _need(_f32c(h, dh, dpre) and h.numel() == dh.numel() == dpre.numel(), "tanh_bwd: f32 buffers")
+    call("zs_tanh_bwd", _p(h), _p(dh), h.numel(), _p(dpre), _s())
+    return dpre
+
+
+def nll_grad_rows(mix, wte, tgt, cnt, dhf, M=None):
+    """zs_nll_grad_rows: dhf[m] = (mix[m] - wte[tgt[m]]) / sum(cnt), zeros without a target."""
+    V, K = wte.shape
+    M = M if M is not None else mix.shape[0]
+    _i32(tgt, "tgt"), _i32(cnt, "cnt")
+    _need(mix.dim() == 2 and dhf.dim() == 2 and mix.shape[1] >= K and dhf.shape[1] >= K
+          and mix.dtype == dhf.dtype == torch.float32 and mix.stride(1) == dhf.stride(1) == 1
+          and mix.shape[0] >= M and dhf.shape[0] >= M and tgt.numel() >= M and wte.is_contiguous()
+          and tgt.is_contiguous() and cnt.is_contiguous(), "nll_grad_rows: buffers")
+    call("zs_nll_grad_rows", _p(mix), mix.stride(0), _p(wte), V, K, _p(tgt), _p(cnt), cnt.numel(), M,
+         _p(dhf), dhf.stride(0), dt(wte), _s())
+    return dhf
+
+
+def nll_loss(sum, cnt, loss):
+    """zs_nll_loss: loss[0] = -sum(sum) / sum(cnt) on the device."""
+    _i32(cnt, "cnt")
+    _need(_f32c(sum, loss) and cnt.is_contiguous() and sum.numel() == cnt.numel()
+          and loss.numel() >= 1, "nll_loss: buffers")
+    call("zs_nll_loss", _p(sum), _p(cnt), cnt.numel(), _p(loss), _s())
+    return loss
+
+
+def soft_grad_rows(dx, hard_len, h_cap, n_soft, B, Smax, d_soft):
+    """zs_soft_grad_rows: the soft-prefix rows of dx [B*Smax, D] -> d_soft [B, n_soft*D]."""
+    _i32(hard_len, "hard_len")
+    D = dx.shape[-1]
+    _need(_f32c(dx) and d_soft.dtype == torch.float32 and d_soft.dim() == 2 and d_soft.stride(1) == 1
+          and d_soft.shape[0] >= B and d_soft.shape[1] >= n_soft * D and dx.numel() >= B * Smax * D
+          and hard_len.numel() >= B, "soft_grad_rows: buffers")
+    call("zs_soft_grad_rows", _p(dx), _p(hard_len), h_cap, n_soft, B, Smax, D, _p(d_soft),
+         d_soft.stride(0), _s())
+    return d_soft
+
+
+def colsum(x, out):
+    """zs_colsum: out[n] = sum_b x[b][n] (row order)."""
+    _need(x.dim() == 2 and x.dtype == out.dtype == torch.float32 and x.stride(1) == 1
+          and out.is_contiguous() and out.numel() >= x.shape[1], "colsum: f32 [B, N] -> [N]")
+    call("zs_colsum", _p(x), x.shape[0], x.shape[1], x.stride(0), _p(out), _s())
+    return out
+
+
+def transpose_cast(x, out):
+    """zs_transpose_cast: x [R, C] f32 -> out [C, R rounded up to 32] (f32 / bf16), zero-filled."""
+    _need(x.dim() == 2 and out.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
+          and out.is_contiguous(), "transpose_cast: x [R, C] f32, out contiguous")
+    R, C = x.shape
+    _need(tuple(out.shape) == (C, -(-R // 32) * 32), f"transpose_cast: out is [{C}, {-(-R // 32) * 32}]")
+    call("zs_transpose_cast", _p(x), R, C, x.stride(0), _p(out), out.shape[1], dt(out), _s())
+    return out
+
+
+def adamw(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, operand=None,
+          step_ctr=None):
+    """zs_adamw: one torch.optim.AdamW update of the f32 master p (moments m, v) from g; operand:
+    the model-dtype copy refreshed in place; step_ctr[0] = step."""
+    _i32(step_ctr, "step_ctr")
+    n = p.numel()
+    _need(_f32c(p, g, m, v) and g.numel() == m.numel() == v.numel() == n, "adamw: f32 buffers of one size")
+    _need(operand is None or (operand.numel() == n and operand.is_contiguous()), "adamw: operand")
+    call("zs_adamw", _p(p), _p(g), _p(m), _p(v), n, float(lr), float(beta1), float(beta2),
+         float(eps), float(weight_decay), int(step), _p(operand),
+         dt(operand) if operand is not None else ZS_F32, _p(step_ctr), _s())
+
+
+def noise_inject(x, out, variance, seed=0, step_ctr=None, row_id=None):
+    """zs_noise_inject: out = normalize(normalize(x) + sqrt(variance) n) (variance 0: a copy)."""
+    _i32(step_ctr, "step_ctr"), _i32(row_id, "row_id")
+    _need(x.dim() == 2 and out.shape == x.shape and x.dtype == out.dtype == torch.float32
+          and x.stride(1) == out.stride(1) == 1, "noise_inject: f32 [B, D]")
+    _need(row_id is None or row_id.numel() >= x.shape[0], "noise_inject: row_id [B]")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if seed >= 1 << 63:
+        seed -= 1 << 64
+    call("zs_noise_inject", _p(x), x.shape[0], x.shape[1], x.stride(0), _p(row_id), _p(step_ctr),
+         seed, float(variance), _p(out), out.stride(0), _s())
+    return out

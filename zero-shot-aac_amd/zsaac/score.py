@@ -92,6 +92,45 @@ class CaptionScores:
                                 "target_ids")))
 
 
+def load_captions(captions: Captions, B: int, T: int, V: int, cap_ids: torch.Tensor,
+                  cap_len: torch.Tensor):
+    """captions -> cap_ids[:B] / cap_len[:B] (device buffers [>= B, T] / [>= B] int32).  Host data
+    is checked here; device tensors by the kernel (CaptionScores.check)."""
+    if (isinstance(captions, tuple) and len(captions) == 2
+            and isinstance(captions[0], torch.Tensor)):
+        ids, ln = captions
+        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] > T or ln.numel() != B:
+            raise ZsError(f"captions: ids [{B}, <= {T}] and len [{B}] expected, got "
+                          f"{tuple(ids.shape)} and {tuple(ln.shape)}")
+        if not ids.is_cuda:
+            if ln.is_cuda:
+                raise ZsError("captions: ids and len on the same side")
+            lens = [int(v) for v in ln.reshape(-1).tolist()]
+            if any(v < 0 or v > ids.shape[1] for v in lens):
+                raise ZsError("captions: a length outside the id tensor")
+            captions = [ids[b, :lens[b]].tolist() for b in range(B)]
+        else:
+            if ids.shape[1] < T:
+                cap_ids[:B].zero_()
+            cap_ids[:B, :ids.shape[1]].copy_(ids)
+            cap_len[:B].copy_(ln.reshape(-1))
+            return
+    if len(captions) != B:
+        raise ZsError(f"captions: {len(captions)} captions for {B} clips")
+    ids = np.zeros((B, T), dtype=np.int32)
+    ln = np.zeros(B, dtype=np.int32)
+    for b, c in enumerate(captions):
+        c = [int(t) for t in c]
+        if len(c) > T:
+            raise ZsError(f"caption {b}: {len(c)} tokens (max_caption_tokens {T})")
+        if any(t < 0 or t >= V for t in c):
+            raise ZsError(f"caption {b}: token id outside [0, {V})")
+        ids[b, :len(c)] = c
+        ln[b] = len(c)
+    cap_ids[:B].copy_(torch.from_numpy(ids))
+    cap_len[:B].copy_(torch.from_numpy(ln))
+
+
 class CaptionScorer:
     """Scores captions of up to ``max_caption_tokens`` tokens for up to ``pipeline.cfg.batch``
     clips per call.  Shares the pipeline's packed GPT-2 weights, mapper and label tables (so it
@@ -131,42 +170,7 @@ class CaptionScorer:
 
     # ------------------------------------------------------------------ inputs
     def _load_captions(self, captions: Captions, B: int):
-        """captions -> cap_ids[:B] / cap_len[:B].  Host data is checked here; device tensors by
-        the kernel (CaptionScores.check)."""
-        T, V = self.Tmax, self.pipe.gpt.V
-        if (isinstance(captions, tuple) and len(captions) == 2
-                and isinstance(captions[0], torch.Tensor)):
-            ids, ln = captions
-            if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] > T or ln.numel() != B:
-                raise ZsError(f"captions: ids [{B}, <= {T}] and len [{B}] expected, got "
-                              f"{tuple(ids.shape)} and {tuple(ln.shape)}")
-            if not ids.is_cuda:
-                if ln.is_cuda:
-                    raise ZsError("captions: ids and len on the same side")
-                lens = [int(v) for v in ln.reshape(-1).tolist()]
-                if any(v < 0 or v > ids.shape[1] for v in lens):
-                    raise ZsError("captions: a length outside the id tensor")
-                captions = [ids[b, :lens[b]].tolist() for b in range(B)]
-            else:
-                if ids.shape[1] < T:
-                    self.cap_ids[:B].zero_()
-                self.cap_ids[:B, :ids.shape[1]].copy_(ids)
-                self.cap_len[:B].copy_(ln.reshape(-1))
-                return
-        if len(captions) != B:
-            raise ZsError(f"captions: {len(captions)} captions for {B} clips")
-        ids = np.zeros((B, T), dtype=np.int32)
-        ln = np.zeros(B, dtype=np.int32)
-        for b, c in enumerate(captions):
-            c = [int(t) for t in c]
-            if len(c) > T:
-                raise ZsError(f"caption {b}: {len(c)} tokens (max_caption_tokens {T})")
-            if any(t < 0 or t >= V for t in c):
-                raise ZsError(f"caption {b}: token id outside [0, {V})")
-            ids[b, :len(c)] = c
-            ln[b] = len(c)
-        self.cap_ids[:B].copy_(torch.from_numpy(ids))
-        self.cap_len[:B].copy_(torch.from_numpy(ln))
+        load_captions(captions, B, self.Tmax, self.pipe.gpt.V, self.cap_ids, self.cap_len)
 
     # ------------------------------------------------------------------ scoring
     def score_wav(self, wav: torch.Tensor, captions: Captions) -> CaptionScores:
